@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Throughput bench of the UniMatch global-matching hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times ONE region of exactly K steps, writes the last step's predictions when --dump-outputs is
+given (DIR/flow_preds_0.npy, float32) and prints the headline fields.  Everything else described below -- the repeated
+regions, ``serial``, the breakdown pass, rooflines, the other precision, box probes, baselines and EPE -- runs with --full.
 
 N > 1: either started by a launcher (``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``: RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment) or, when run as plain ``python``, this script launches its
@@ -24,11 +28,11 @@ of 4 pairs on two HIP streams -- the samples of a batch are independent, and the
 forward of its samples.  ``--streams N`` forces a count (1 = one forward of 8); the line carries the one-forward figure as ``serial`` either way.
 
 The headline region is EVENT-FREE (round 4): ``value`` / ``ms_per_step`` come from K steps bracketed by barrier + synchronize with
-no per-kernel event inside.  Round 6: that region is run three times back to back and the MEDIAN region is reported (``regions``,
-``region_ms_per_step_min_max``).  Directly after it a BREAKDOWN pass runs the same K steps twice with the library's per-kernel hipEvents
+no per-kernel event inside.  With --full that region is run three times back to back and the MEDIAN region is reported (``regions``,
+``region_ms_per_step_min_max``), and directly after it a BREAKDOWN pass runs the same K steps twice with the library's per-kernel hipEvents
 (``um_timing_*``, recorded on the launch stream): once timing only the launches inside the CNN encoder, once only those outside it.
 
-Extra objects on the line:
+Extra objects on the line (--full only):
   serial                throughput of the same K steps as ONE forward of the per-GPU batch per step (``config.streams`` = 1 when the
                         headline itself ran that way): the mode of every per-kernel figure below -- in the concurrent mode the
                         durations of kernels that share the GPU overlap and do not price a kernel.
@@ -64,6 +68,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -72,7 +77,8 @@ sys.path.insert(0, ROOT)
 PEAK_MFMA_16BIT = 2.5e15        # dense bf16/fp16 MFMA peak of MI355X (MI355X_MICROARCH.md)
 HEIGHT, WIDTH, BATCH = 512, 768, 8
 UM_K_COUNT = 12                 # include/unimatch_hip.h
-REGIONS = 3                     # the K-step headline region is repeated this many times inside the run; `value` is the MEDIAN region
+REGIONS = 3                     # --full: the K-step headline region is repeated this many times; `value` is the MEDIAN region
+DUMP_BYTES = 64 << 20           # --dump-outputs: at most this much in all
 PMC_FILE = os.path.join(ROOT, 'profiles', 'pmc_current.json')
 
 
@@ -99,6 +105,13 @@ def parse():
                     help='replay the HIP graph of the forward (unimatch_amd.graph) in the timed steps instead of launching eagerly '
                          '(measured on MI355X at config 2: 817.5 / 817.0 pairs/s against 818.6 / 819.1 eager -- the step is GPU-bound, '
                          'the default stays eager)')
+    ap.add_argument('--full', action='store_true',
+                    help=f'everything beyond the headline: the median of {REGIONS} regions, `serial`, the breakdown pass, rooflines, the '
+                         'key-tile census, the other precision, box probes, the CPU / ROCm-eager baselines and EPE.  Without it the run '
+                         'times ONE region of exactly --steps steps and prints the headline fields only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32): '
+                         'flow_preds_0 = the whole job\'s predictions [pairs, 2, H, W]; beyond 64 MB a fixed seeded subset of the pairs')
     ap.add_argument('--cpu-iters', type=int, default=8)
     ap.add_argument('--set', action='append', default=[], metavar='Class.attr=value',
                     help='A/B knob for tools/ab_bench.py: set a class attribute of HipOps / CNNEncoder before the run, e.g. '
@@ -117,6 +130,18 @@ def apply_knobs(specs):
             raise SystemExit(f'bench.py --set: unknown knob {target}')
         old = getattr(classes[cls], attr)
         setattr(classes[cls], attr, type(old)(int(value)) if isinstance(old, (bool, int)) else type(old)(value))
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32.  An array over its share of DUMP_BYTES keeps a fixed seeded
+    subset of its pairs (dim 0) in ascending order, so two builds run with the same arguments write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float().cpu()
+        keep = DUMP_BYTES // len(arrays) // (t[0].numel() * 4)
+        if keep < t.shape[0]:
+            t = t[torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values]
+        np.save(os.path.join(path, name + '.npy'), t.numpy())
 
 
 def collect(lib, kid):
@@ -483,11 +508,72 @@ def main():
         enc_wall = sum(a.elapsed_time(b_) for a, b_ in spans) / max(len(spans), 1)
         return out[0], out[1], enc_wall
 
-    elapsed, pred, launch_mode = timed(args.precision, args.steps, args.warmup, regions=REGIONS)
+    def finish(line):
+        """Close the collective; rank 0 prints the line."""
+        if distributed:
+            gather.close()
+            dist.destroy_process_group()
+        if rank != 0:
+            return
+        # RCCL writes its version banner to C stdout (buffered until exit): flush it first so that the JSON line is the LAST line
+        try:
+            ctypes.CDLL(None).fflush(None)
+        except OSError:
+            pass
+        sys.stdout.write(json.dumps(line) + '\n')
+        sys.stdout.flush()
+
+    regions = REGIONS if args.full else 1
+    elapsed, pred, launch_mode = timed(args.precision, args.steps, args.warmup, regions=regions)
     headline_parts = concurrent['parts']
     headline_regions = [round(v, 3) for v in region_spread]
     median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
     spread_ms = (step_ms[0], step_ms[-1])
+    if args.dump_outputs and rank == 0:
+        # what the caller of the last timed step holds: the gathered predictions of every rank (cfg2 on N ranks, rank-major),
+        # ShardedUniMatch's [global batch, ...] (cfg4), the model's own flow_preds[0] (one GPU)
+        out = gathered[(pending['i'] - 1) & 1].reshape(world * b, 2, HEIGHT, WIDTH) if side is not None else pred
+        dump_outputs(args.dump_outputs, {'flow_preds_0': out})
+    rccl_ranks = gather.ranks() if gather is not None else 1
+    pairs = gb * args.steps
+    value = pairs / elapsed
+    if cfg4:
+        workload = (f'GMFlow scale-2 + 6 refinements (BASELINE.json configs[3]), GLOBAL batch {gb} x {HEIGHT}x{WIDTH} sharded over '
+                    f'{world} rank(s) ({b} pairs on rank 0), swin K=[2,8], global + local (r=4) correlation, global + local propagation, '
+                    'random-init weights')
+    else:
+        workload = (f'GMFlow scale-1 flow, batch {b} x {HEIGHT}x{WIDTH} per GPU, swin K=2, global '
+                    'correlation + global propagation, random-init weights')
+    line = {
+        'metric': 'image_pairs_per_sec', 'value': round(value, 3), 'unit': 'pairs/s', 'n_gpus': world,
+        'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 3),
+        'ms_per_step_median': round(median_ms, 3), 'ms_per_step_min_max': [round(spread_ms[0], 3), round(spread_ms[1], 3)],
+        'regions': regions, 'region_ms_per_step_min_max': headline_regions,
+        'pairs_per_sec_at_median': round((gb if cfg4 else b) / (median_ms * 1e-3), 2),
+        'higher_is_better': True, 'scaling': 'strong' if cfg4 else 'weak', 'vs_baseline': None,
+        'dtype': 'f16x2' if args.precision == 'exact' else 'bf16',
+        'data': 'synthetic', 'rccl_ranks': rccl_ranks, 'collective': gather_kind if distributed else None,
+        'config': {'workload': workload,
+                   'per_gpu_batch': b, 'global_batch': gb, 'precision': args.precision, 'launch_mode': launch_mode,
+                   'streams': headline_parts,
+                   'precision_note': 'exact = fp16 hi+lo split MFMA operands (3 products), fp32 accumulate/softmax; every '
+                                     'GEMM / convolution of the forward runs on the library\'s own split-fp16 MFMA kernels '
+                                     '(no MIOpen, hipBLASLt or rocBLAS kernel in the forward)',
+                   'parallelism': ((f'dp{world} (batch-sharded through ShardedUniMatch, um_allgather_preds = ncclAllGather of the predictions on the compute stream)'
+                                    if cfg4 else
+                                    f'dp{world} (batch-sharded, um_allgather_preds = ncclAllGather of predictions, side stream)')
+                                   if distributed else 'single GPU'),
+                   'weights': 'synth_state_dict(seed 326): per-parameter seeded generator with the reference initialisers\' '
+                              'statistics (xavier-uniform / kaiming-normal), rebuilt identically on any box'},
+        'full': args.full,
+        'timing_note': 'value / ms_per_step: event-free region (barrier + synchronize around exactly K steps), eager launches (--graph '
+                       'replays the forward as a HIP graph; config.launch_mode).  The step is model(...): UniMatch.forward\'s own plan '
+                       '(or --streams N).  --full adds the rest of the line (median of several regions, serial, breakdown, rooflines, '
+                       'baselines)',
+    }
+    if not args.full:
+        finish(line)
+        return
     serial = None
     if 'concurrent' in launch_mode:                                # the same K steps as ONE forward per step (what the breakdown pass times)
         s_el, _, _ = timed(args.precision, args.steps, 2, streams=1)
@@ -508,12 +594,9 @@ def main():
         e_el, e_pred, _ = timed(other, args.steps, max(2, args.warmup // 2))
         extra = (e_el, e_pred) + breakdown(args.steps)
         model.set_precision(args.precision)
-    rccl_ranks = gather.ranks() if gather is not None else 1
 
     if rank != 0:
-        if distributed:
-            gather.close()
-            dist.destroy_process_group()
+        finish(None)
         return
     box = box_probe(lib, dev)
     sustained = box['mfma_sustained_tflops'] * 1e12
@@ -668,37 +751,8 @@ def main():
                     'epe_vs_fp64_truth': epe_other,
                     'note': 'same workload and steps in the other operand precision; reported beside the headline, not a parity claim'}
 
-    pairs = gb * args.steps
-    value = pairs / elapsed
-    if cfg4:
-        workload = (f'GMFlow scale-2 + 6 refinements (BASELINE.json configs[3]), GLOBAL batch {gb} x {HEIGHT}x{WIDTH} sharded over '
-                    f'{world} rank(s) ({b} pairs on rank 0), swin K=[2,8], global + local (r=4) correlation, global + local propagation, '
-                    'random-init weights')
-    else:
-        workload = (f'GMFlow scale-1 flow, batch {b} x {HEIGHT}x{WIDTH} per GPU, swin K=2, global '
-                    'correlation + global propagation, random-init weights')
-    line = {
-        'metric': 'image_pairs_per_sec', 'value': round(value, 3), 'unit': 'pairs/s', 'n_gpus': world,
-        'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 3),
-        'ms_per_step_median': round(median_ms, 3), 'ms_per_step_min_max': [round(spread_ms[0], 3), round(spread_ms[1], 3)],
-        'regions': REGIONS, 'region_ms_per_step_min_max': headline_regions,
+    line.update({
         'box': box,
-        'pairs_per_sec_at_median': round((gb if cfg4 else b) / (median_ms * 1e-3), 2),
-        'higher_is_better': True, 'scaling': 'strong' if cfg4 else 'weak', 'vs_baseline': None,
-        'dtype': 'f16x2' if args.precision == 'exact' else 'bf16',
-        'data': 'synthetic', 'rccl_ranks': rccl_ranks, 'collective': gather_kind if distributed else None,
-        'config': {'workload': workload,
-                   'per_gpu_batch': b, 'global_batch': gb, 'precision': args.precision, 'launch_mode': launch_mode,
-                   'streams': headline_parts,
-                   'precision_note': 'exact = fp16 hi+lo split MFMA operands (3 products), fp32 accumulate/softmax; every '
-                                     'GEMM / convolution of the forward runs on the library\'s own split-fp16 MFMA kernels '
-                                     '(no MIOpen, hipBLASLt or rocBLAS kernel in the forward)',
-                   'parallelism': ((f'dp{world} (batch-sharded through ShardedUniMatch, um_allgather_preds = ncclAllGather of the predictions on the compute stream)'
-                                    if cfg4 else
-                                    f'dp{world} (batch-sharded, um_allgather_preds = ncclAllGather of predictions, side stream)')
-                                   if distributed else 'single GPU'),
-                   'weights': 'synth_state_dict(seed 326): per-parameter seeded generator with the reference initialisers\' '
-                              'statistics (xavier-uniform / kaiming-normal), rebuilt identically on any box'},
         'roofline': roof, 'roofline_global_corr': roof2, 'roofline_ffn': roof3,
         'hot_path_ms_per_step': hot_ms, 'encoder_ms_per_step': enc_ms,
         'encoder_wall_ms_per_step': round(enc_wall_ms, 3),
@@ -720,17 +774,8 @@ def main():
         'cpu_baseline': cpu, 'rocm_eager_baseline': eager, 'epe': epe or None,
         'speedup_vs_cpu_port': None if cpu is None else round(value / cpu['value'], 1),
         'speedup_vs_rocm_eager': None if not eager or not eager.get('value') else round(value / eager['value'], 1),
-    }
-    if distributed:
-        gather.close()
-        dist.destroy_process_group()
-    # RCCL writes its version banner to C stdout (buffered until exit): flush it first so that the JSON line is the LAST line
-    try:
-        ctypes.CDLL(None).fflush(None)
-    except OSError:
-        pass
-    sys.stdout.write(json.dumps(line) + '\n')
-    sys.stdout.flush()
+    })
+    finish(line)
 
 
 if __name__ == '__main__':

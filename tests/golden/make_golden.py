@@ -1,6 +1,6 @@
 """Mint golden fixtures from the REAL reference (runs only where /root/reference exists).
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [fixture ...]
 
 The reference has no tests and no golden vectors of its own, so its behaviour on the
 hot path is pinned here by executing it: every hot-path function (unimatch/attention.py, matching.py,
@@ -9,6 +9,7 @@ on seeded inputs with seeded weights (``unimatch_amd.synth``); inputs that canno
 seed, and all outputs, are stored as small ``.npz`` files next to this script.  The fixtures travel to the
 GPU box; the reference does not.
 """
+import hashlib
 import os
 import sys
 import warnings
@@ -248,11 +249,44 @@ def gold_formats():
     save('formats', **out)
 
 
+# ----------------------------------------------------------------------------------------------- constructor weights
+def tensor_digest(t):
+    """sha256 over dtype, shape and raw bytes: equal digests <=> bit-identical tensors (tests/test_host_logic_cpu.py)."""
+    t = t.detach().cpu().contiguous()
+    h = hashlib.sha256(f'{t.dtype}{tuple(t.shape)}'.encode())
+    h.update(t.numpy().tobytes())
+    return h.hexdigest()
+
+
+def gold_constructor():
+    """The reference constructor's state_dict after ``torch.manual_seed(326)`` (main_flow.py:56), per config: parameter names
+    in registration order and one digest per tensor (the weights themselves would be tens of MB)."""
+    out = {}
+    for name in sorted(CONFIGS):
+        torch.manual_seed(326)
+        sd = RefUniMatch(**CONFIGS[name][0]).state_dict()
+        out[f'{name}.keys'] = np.array(list(sd))
+        out[f'{name}.sha256'] = np.array([tensor_digest(v) for v in sd.values()])
+    save('constructor_seed326', **out)
+
+
+# ----------------------------------------------------------------------------------------------- dilated cost volume
+def gold_dilation():
+    """local_correlation_with_flow(..., dilation=d) (matching.py:86-123) for d = 1, 2, 3: no caller of the reference uses d != 1,
+    the oracle's restatement of it checks um_local_corr_with_flow_dilated."""
+    g = torch.Generator().manual_seed(7)
+    f0, f1 = torch.randn(2, 128, 12, 16, generator=g), torch.randn(2, 128, 12, 16, generator=g)
+    flow = torch.randn(2, 2, 12, 16, generator=g) * 3
+    out = {f'dilation{d}': rmat.local_correlation_with_flow(f0, f1, flow, 4, dilation=d) for d in (1, 2, 3)}
+    save('dilation', f0=f0, f1=f1, flow=flow, **out)
+
+
+GOLD = {'position': gold_position, 'attention': gold_attention, 'transformer': gold_transformer, 'matching': gold_matching,
+        'propagation': gold_propagation, 'e2e': gold_e2e, 'formats': gold_formats, 'constructor_seed326': gold_constructor,
+        'dilation': gold_dilation}
+
+
 if __name__ == '__main__':
-    gold_position()
-    gold_attention()
-    gold_transformer()
-    gold_matching()
-    gold_propagation()
-    gold_e2e()
-    gold_formats()
+    # python tests/golden/make_golden.py [fixture ...]   (default: every fixture)
+    for fixture in sys.argv[1:] or list(GOLD):
+        GOLD[fixture]()

@@ -2,6 +2,7 @@
 state_dict names), the per-scale orchestration with the oracle injected as hot-path backend, the C-ABI
 library (loads, exports every declared symbol) and the loud failure when no GPU / extension is present."""
 import ctypes
+import hashlib
 import inspect
 import os
 import re
@@ -101,26 +102,28 @@ def test_state_dict_names_and_param_counts():
     assert 'upsampler.0.weight' not in sd
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/unimatch'), reason='needs the reference checkout (build container only)')
+def tensor_digest(t):
+    """sha256 over dtype, shape and raw bytes -- the digest tests/golden/make_golden.py stores for the reference's tensors."""
+    t = t.detach().cpu().contiguous()
+    h = hashlib.sha256(f'{t.dtype}{tuple(t.shape)}'.encode())
+    h.update(t.numpy().tobytes())
+    return h.hexdigest()
+
+
 @pytest.mark.parametrize('name', sorted(CONFIGS))
-def test_constructor_weights_match_reference_seed_326(name):
+def test_constructor_weights_match_reference_seed_326(golden, name):
     """SURVEY.md 8(d) prescribes the weights ``torch.manual_seed(326)`` (main_flow.py:56) + the reference constructor.  This
     package's constructor registers and initialises its parameters in the same order with the same initialisers, so the same seed
     gives BIT-IDENTICAL weights -- which is what lets the GPU box (no reference there) rebuild the reference-constructor
-    weight set (tools/parity_fullsize.py, weight set ``ctor326``)."""
-    sys.path.insert(0, '/root/reference')
-    try:
-        from unimatch.unimatch import UniMatch as RefUniMatch
-    finally:
-        sys.path.remove('/root/reference')
+    weight set (tools/parity_fullsize.py, weight set ``ctor326``).  The reference's side: parameter names in registration order
+    and a digest of every tensor, from tests/golden/constructor_seed326.npz."""
+    g = golden('constructor_seed326')._z
     ck = CONFIGS[name][0]
     torch.manual_seed(326)
-    ref = RefUniMatch(**ck).state_dict()
-    torch.manual_seed(326)
     own = UniMatch(**ck).state_dict()
-    assert list(ref) == list(own)
-    for k in ref:
-        assert torch.equal(ref[k], own[k]), k
+    assert list(g[f'{name}.keys']) == list(own)
+    for k, want in zip(g[f'{name}.keys'], g[f'{name}.sha256']):
+        assert tensor_digest(own[str(k)]) == want, k
 
 
 def test_reference_error_behaviour():

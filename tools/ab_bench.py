@@ -52,7 +52,7 @@ def main():
         for label, (extra_env, extra_args) in variants:
             env = dict(os.environ)
             env.update(extra_env)
-            out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--no-cpu-baseline', '--no-fast', '--steps', steps] + extra_args,
+            out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-cpu-baseline', '--no-fast', '--steps', steps] + extra_args,
                                  capture_output=True, text=True, env=env, cwd=ROOT)
             try:
                 d = json.loads(out.stdout.strip().splitlines()[-1])

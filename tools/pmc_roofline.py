@@ -33,7 +33,7 @@ def main():
     dirty = bool(subprocess.run(['git', 'status', '--porcelain', 'unimatch_amd/csrc'], capture_output=True, text=True,
                                 cwd=ROOT).stdout.strip())
     out = {'git': git + ('+dirty' if dirty else ''),
-           'note': 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (separate runs, --kernel-trace only) over `python bench.py '
+           'note': 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (separate runs, --kernel-trace only) over `python bench.py --full '
                    '--steps 3 --warmup 2 --no-cpu-baseline`; read bytes = 2 x FETCH_SIZE KiB x 1024 (gfx950 correction), write '
                    'bytes = WRITE_SIZE KiB x 1024; means per dispatch'}
     if '--from-r01' in sys.argv:

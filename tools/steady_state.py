@@ -1,8 +1,8 @@
 """Per-kernel time of the LAST steps of a `rocprofv3 --kernel-trace --output-format csv` run of bench.py.
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/trace -o t -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline
-    python tools/steady_state.py gpurun_out/trace/t_kernel_trace.csv 10 > profiles/rNN_steady_state_breakdown.txt
+    rocprofv3 --kernel-trace --output-format csv -d /tmp/trace -o t -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
+    python tools/steady_state.py /tmp/trace/t_kernel_trace.csv 10 > profiles/rNN_steady_state_breakdown.txt
 
 A step starts at the stem's `pack7_kernel` launch (one per forward); the last N steps before the census forward / box probes that
 end a bench.py run are summed per kernel name.
