@@ -485,6 +485,22 @@ int um_convex_upsample(const float* flow, const float* mask, float* up, int batc
 int um_flow_warp(const float* feature_tokens, const float* flow, float* out_tokens, int batch, int h, int w, int channels,
                  void* stream);
 
+/* Video post-processing (csrc/video.hip), applied to a batch of predicted flows; both memory-bound, no state between calls.
+ *   um_fwd_bwd_occlusion  forward_backward_consistency_check (unimatch/geometry.py:75-96) in one launch: fwd, bwd [B,2,H,W] fp32 ->
+ *                         occ_fwd, occ_bwd [B,H,W] fp32 in {0, 1}.  Per pixel p and direction: the other flow sampled at p + flow(p)
+ *                         (bilinear, zeros outside, grid_sample align_corners=True with the reference's normalise / un-normalise
+ *                         round trip), occluded where |flow + warped| > alpha (|fwd| + |bwd|) + beta.  H, W >= 2.
+ *   um_flow_to_rgb        flow_to_image (utils/flow_viz.py:231-254) per image: flow [B,2,H,W] fp32 -> rgb [B,H,W,3] uint8.  Unknown
+ *                         flow (|u| or |v| > 1e7) is black; each image is normalised by its OWN maximum |flow| plus float64 eps (-1
+ *                         when that maximum is NaN, as max(-1, np.max(rad)) gives); Middlebury wheel of 55 hues, float64 from the
+ *                         normalisation on.  Two launches (partial maxima into `workspace`, then colour): no atomics, no counters, every
+ *                         workspace slot is rewritten by each call.  workspace >= um_flow_to_rgb_workspace_bytes(batch, h, w) (0 for
+ *                         bad sizes). */
+int um_fwd_bwd_occlusion(const float* fwd, const float* bwd, float* occ_fwd, float* occ_bwd, int batch, int h, int w, float alpha,
+                         float beta, void* stream);
+size_t um_flow_to_rgb_workspace_bytes(int batch, int h, int w);
+int um_flow_to_rgb(const float* flow, unsigned char* rgb, int batch, int h, int w, void* workspace, size_t ws_bytes, void* stream);
+
 /* The per-scale loop's small glue ops (round 3: they were torch calls):
  *   um_flow_upsample2x  out[B,V,2h,2w] = mult * bilinear_up2(flow[B,V,h,w]), align_corners = True -- unimatch/unimatch.py:162-163
  *                       (F.interpolate(..., scale_factor=2, mode='bilinear', align_corners=True) * 2: pass mult = 2)

@@ -122,6 +122,21 @@ def write_png16(filename, arr):
         f.write(_png_chunk(b'IEND', b''))
 
 
+def write_png8(filename, arr):
+    """arr: uint8 [H, W] (grey) or [H, W, 3] (RGB) -- what the reference saves through PIL (flow colourings, occlusion masks)."""
+    arr = np.asarray(arr)
+    assert arr.dtype == np.uint8 and (arr.ndim == 2 or (arr.ndim == 3 and arr.shape[2] == 3))
+    h, w = arr.shape[:2]
+    color_type = 0 if arr.ndim == 2 else 2
+    rows = np.ascontiguousarray(arr).reshape(h, -1)
+    raw = np.concatenate([np.zeros((h, 1), np.uint8), rows], 1).tobytes()     # filter type 0 on every scanline
+    with open(filename, 'wb') as f:
+        f.write(b'\x89PNG\r\n\x1a\n')
+        f.write(_png_chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, color_type, 0, 0, 0)))
+        f.write(_png_chunk(b'IDAT', zlib.compress(raw, 6)))
+        f.write(_png_chunk(b'IEND', b''))
+
+
 def read_png16(filename):
     with open(filename, 'rb') as f:
         blob = f.read()

@@ -21,6 +21,7 @@ What is different inside:
 There is no CPU or PyTorch fallback for the hot path (the stock ``nn.Module`` convolution code only runs on CPU tensors).
 """
 import math
+import weakref
 
 import torch
 import torch.nn as nn
@@ -486,6 +487,149 @@ class UniMatch(nn.Module):
             self._runner = PartRunner()
         return self._runner.run(self, parts, img0, img1, kw)
 
+    # ------------------------------------------------------------------ video: consecutive frames
+    def _carry_state(self, frames):
+        """What a carry is valid for: the model and backend objects (weak references), device, geometry, the backend's cache
+        generation and the parameters' identity / versions."""
+        ops = self._ops
+        params = tuple((id(p), p.data_ptr(), p._version) for p in self.parameters())
+        return ((weakref.ref(self), None if ops is None else weakref.ref(ops)),
+                (str(frames.device), tuple(frames.shape[1:]), getattr(ops, 'cache_generation', None), params))
+
+    def _carry_valid(self, carry, frames):
+        refs, key = carry['state']
+        now_refs, now_key = self._carry_state(frames)
+        return (refs[0]() is self and (refs[1] is None) == (now_refs[1] is None) and (refs[1] is None or refs[1]() is self._ops)
+                and key == now_key)
+
+    def forward_sequence(self, frames, attn_type=None, attn_splits_list=None, corr_radius_list=None, prop_radius_list=None,
+                         num_reg_refine=1, pred_bidir_flow=False, consistency_check=False, colorize=False, pairs_per_launch=8,
+                         carry=None, task='flow'):
+        """Optical flow of every pair (t, t+1) of a frame sequence ``frames [T, 3, H, W]`` (raw 0..255), each frame encoded ONCE.
+
+        The reference's ``inference_flow`` (evaluate_flow.py:640-831) runs the model on each pair, so every interior frame goes through
+        the CNN encoder twice.  The encoder is strictly per image, so here a chunk of ``pairs_per_launch`` pairs encodes only the frames
+        not encoded yet (``B + 1`` images for ``B`` pairs, ``B`` with the previous chunk's last frame) and the match step runs on the
+        stream ``[F[0:B]; F[1:B+1]]`` built by one concatenation per scale.  ``carry`` (the previous call's ``out['carry']``) continues a
+        long video fed in pieces: its frame pairs with ``frames[0]``.  A carry made under another model, backend, device, geometry,
+        backend cache generation or parameter version is not trusted: its stored frame is encoded again.
+
+        Returns ``{'flow': [P, 2, H, W], 'carry': ...}`` with ``P = T - 1`` (``T`` with a carry), plus ``'flow_bwd'`` with
+        ``pred_bidir_flow``, ``'occ_fwd'`` / ``'occ_bwd'`` ``[P, H, W]`` float with ``consistency_check`` (the reference's
+        forward_backward_consistency_check) and ``'flow_rgb'`` (``'flow_bwd_rgb'``) ``[P, H, W, 3]`` uint8 with ``colorize`` (its
+        flow_to_image, each image normalised by its own maximum)."""
+        if self.training:
+            raise RuntimeError('this module implements inference only: call .eval()')
+        if task != 'flow':
+            raise NotImplementedError('forward_sequence is optical flow only')
+        if consistency_check and not pred_bidir_flow:
+            raise AssertionError('consistency_check needs pred_bidir_flow=True (as the reference asserts)')
+        if frames.dim() != 4 or frames.shape[1] != 3:
+            raise ValueError(f'frames: expected [T, 3, H, W], got {tuple(frames.shape)}')
+        if int(pairs_per_launch) < 1:
+            raise ValueError('pairs_per_launch must be >= 1')
+        if carry is not None and tuple(carry['frame'].shape[1:]) != tuple(frames.shape[1:]):
+            raise ValueError(f'carry holds a {tuple(carry["frame"].shape[2:])} frame, frames are {tuple(frames.shape[2:])}')
+        pairs = frames.shape[0] - (0 if carry is not None else 1)
+        if pairs < 1:
+            raise ValueError('no frame pair: give at least two frames, or one with a carry')
+        kw = dict(attn_type=attn_type if attn_type is not None else '', attn_splits_list=attn_splits_list,
+                  corr_radius_list=corr_radius_list, prop_radius_list=prop_radius_list, num_reg_refine=num_reg_refine,
+                  pred_bidir_flow=pred_bidir_flow, task='flow')
+        assert len(attn_splits_list) == len(corr_radius_list) == len(prop_radius_list) == self.num_scales
+        import contextlib
+        from . import video
+        dev = frames.device
+        ops = self.ops
+        if self.check_weights:
+            self._check_weight_print()
+        if frames.is_cuda and self.check_range and getattr(ops, 'mode', 1) == 0:
+            from . import _abi
+            _abi.check_operand_range('an earlier forward of this process: ')
+        guard = torch.cuda.device(dev) if frames.is_cuda else contextlib.nullcontext()
+        step = int(pairs_per_launch)
+        out = {k: [] for k in ('flow', 'flow_bwd', 'occ_fwd', 'occ_bwd', 'flow_rgb', 'flow_bwd_rgb')}
+        with guard, torch.no_grad():
+            prev = None                                   # per-scale features [1, C, h, w] of the frame before frames[i]
+            if carry is not None:
+                if self._carry_valid(carry, frames):
+                    prev = carry['features']
+                else:                                     # stale: the stored frame is encoded with the first chunk
+                    frames = torch.cat([carry['frame'].to(dev), frames], 0)
+            i = 0                                         # first frame of the next chunk's new frames
+            while i < frames.shape[0] - (1 if prev is None else 0):
+                # the chunk's frames: [prev] + the new ones -- B + 1 frames for B pairs, the first one carried when it was encoded already
+                new = frames[i:i + step + (1 if prev is None else 0)]
+                feats = self._encode((new,))
+                chunk = [([] if prev is None else [p]) + [f] for p, f in zip(prev or feats, feats)]
+                nb = new.shape[0] - (1 if prev is None else 0)
+                i += new.shape[0]
+                pred = self._match_pairs(chunk, nb, kw)
+                prev = [f[f.shape[0] - 1:] for f in feats]
+                fwd = pred[:nb]
+                out['flow'].append(fwd)
+                if pred_bidir_flow:
+                    bwd = pred[nb:]
+                    out['flow_bwd'].append(bwd)
+                    if consistency_check:
+                        occ_f, occ_b = video.forward_backward_consistency_check(fwd, bwd)
+                        out['occ_fwd'].append(occ_f)
+                        out['occ_bwd'].append(occ_b)
+                if colorize:
+                    out['flow_rgb'].append(video.flow_to_image(fwd))
+                    if pred_bidir_flow:
+                        out['flow_bwd_rgb'].append(video.flow_to_image(bwd))
+            last = frames[frames.shape[0] - 1:]
+            result = {k: v[0] if len(v) == 1 else torch.cat(v, 0) for k, v in out.items() if v}
+            result['carry'] = {'features': [p.clone() for p in prev], 'frame': last.clone(), 'state': self._carry_state(frames)}
+        return result
+
+    def _match_pairs(self, chunk, nb, kw):
+        """The match step of the ``nb`` pairs of consecutive frames whose features are ``chunk[s]`` (per scale, a list of pieces
+        ``[N_i, C, h, w]`` that together hold the ``nb + 1`` frames in order) -> predictions ``[bidir * nb, 2, H, W]`` in the reference's
+        [forward; backward] order.  The stream ``[F[lo:hi]; F[lo+1:hi+1]]`` of pairs lo .. hi-1 is ONE concatenation per scale.  Where
+        ``streams.forward_parts`` says so, the pairs run as concurrent parts on the process-wide side streams (``streams.PartRunner``)."""
+        def frames_of(pieces, a, b):                  # the pieces that hold frames a .. b-1 of the chunk
+            out, base = [], 0
+            for t in pieces:
+                lo, hi = max(a, base), min(b, base + t.shape[0])
+                if lo < hi:
+                    out.append(t[lo - base:hi - base])
+                base += t.shape[0]
+            return out
+
+        def stream(lo, hi):
+            return [torch.cat(frames_of(pieces, lo, hi) + frames_of(pieces, lo + 1, hi + 1), 0) for pieces in chunk]
+
+        ref = chunk[-1][-1]
+        h8, w8 = ref.shape[-2:]
+        parts = self.launch_parts
+        if parts is None:
+            parts = 1
+            if ref.is_cuda and self.debug_taps is None:
+                from .streams import forward_parts
+                parts = forward_parts('flow', kw['attn_type'], self.num_scales, self.reg_refine, nb,
+                                      self.upsample_factor * h8, self.upsample_factor * w8)
+        parts = min(int(parts), nb)
+        if parts <= 1:
+            return self._match(stream(0, nb), nb, **kw)['flow_preds'][0]
+        if self._runner is None:
+            from .streams import PartRunner
+            self._runner = PartRunner()
+        from .dist import shard_bounds
+        bidir = 2 if kw['pred_bidir_flow'] else 1
+
+        def prepare(r):
+            lo, hi = shard_bounds(nb, r, parts)
+            return stream(lo, hi), hi - lo
+
+        def compute(r, ins):
+            return self._match(ins[0], ins[1], **kw)['flow_preds']
+
+        small = tuple(sorted((k, tuple(v) if isinstance(v, list) else v) for k, v in kw.items()))
+        key = ('sequence', parts, nb, tuple(ref.shape[1:]), str(ref.device), small, sum(p._version for p in self.parameters()))
+        return self._runner.run_parts(self, parts, nb, bidir, key, ref.device, prepare, compute)['flow_preds'][0]
+
     def _forward_one(self, img0, img1, attn_type=None, attn_splits_list=None, corr_radius_list=None,
                      prop_radius_list=None, num_reg_refine=1, pred_bidir_flow=False, task='flow', intrinsics=None,
                      pose=None, min_depth=1. / 0.5, max_depth=1. / 10, num_depth_candidates=64,
@@ -518,161 +662,181 @@ class UniMatch(nn.Module):
         if img1.device != dev:
             raise ValueError(f'img0 is on {dev} and img1 on {img1.device}')
         with guard, torch.no_grad():
-            input_norm = None
-            if task == 'flow':                  # stereo / depth loaders normalise already (unimatch.py:122-124)
-                if self.backbone.takes_raw_images(ops, img0):
-                    input_norm = (_IMAGENET_MEAN, _IMAGENET_STD)            # folded into the stem's image packing
-                else:
-                    mean, std = self._constants(dev)
-                    img0, img1 = (img0 / 255. - mean) / std, (img1 / 255. - mean) / std
-            feats = self.backbone(torch.cat([img0, img1], 0), ops, input_norm)[::-1]    # low -> high resolution
-            nb = img0.shape[0]
-            flow, pred = None, None
-            for s in range(self.num_scales):
-                m0, m1 = feats[s][:nb], feats[s][nb:]                         # [B, C, h, w]
-                both = None
-                if pred_bidir_flow and s > 0:
-                    m0, m1 = torch.cat([m0, m1], 0), torch.cat([m1, m0], 0)
-                    ori0, ori1 = _to_tokens(m0), _to_tokens(m1)               # pre-position, pre-warp tokens
-                else:
-                    both = _to_tokens(feats[s])                               # the encoder's batched output is [f0; f1]
-                    ori0, ori1 = both[:nb], both[nb:]
-                h, w = m0.shape[-2:]
-                up = self.upsample_factor * 2 ** (self.num_scales - 1 - s)
-                if task == 'depth':
-                    k_cur = intrinsics.clone()
-                    k_cur[:, :2] = k_cur[:, :2] / up
-                if s > 0:
-                    if hasattr(ops, 'flow_upsample2x') and flow.is_cuda:
-                        flow = ops.flow_upsample2x(flow, 2.0)          # unimatch.py:162-163 on um_flow_upsample2x
-                    else:
-                        flow = F.interpolate(flow, scale_factor=2, mode='bilinear', align_corners=True) * 2
-                tok1 = ori1
-                if flow is not None:
-                    assert task != 'depth'
-                    disp = torch.cat([-flow, torch.zeros_like(flow)], 1) if task == 'stereo' else flow
-                    if hasattr(ops, 'flow_warp') and ori1.is_cuda:
-                        tok1 = ops.flow_warp(ori1, disp.contiguous(), h, w)
-                    else:
-                        tok1 = _to_tokens(_warp(m1, disp))
-                splits, prop_r = attn_splits_list[s], prop_radius_list[s]
-                pos = self._position(h, w, splits, dev)
-                if self.debug_taps is not None:
-                    self.debug_taps[f'backbone0_s{s}'], self.debug_taps[f'backbone1_s{s}'] = m0, m1
-                if tok1 is ori1 and both is not None:
-                    # no warp, no bidirectional stacking: the stream [f0; f1] is the encoder's output -- one position add on
-                    # the whole of it instead of two adds and a concatenation
-                    tok0, tok1 = self.transformer(ops, None, None, h, w, attn_type, splits, stream=both + pos)
-                else:
-                    tok0, tok1 = self.transformer(ops, ori0 + pos, tok1 + pos, h, w, attn_type, splits)
-                if self.debug_taps is not None:
-                    self.debug_taps[f'f0_s{s}'], self.debug_taps[f'f1_s{s}'] = _to_map(tok0, h, w), _to_map(tok1, h, w)
+            feats = self._encode((img0, img1), task)
+            return self._match(feats, img0.shape[0], attn_type=attn_type, attn_splits_list=attn_splits_list,
+                               corr_radius_list=corr_radius_list, prop_radius_list=prop_radius_list, num_reg_refine=num_reg_refine,
+                               pred_bidir_flow=pred_bidir_flow, task=task, intrinsics=intrinsics, pose=pose, min_depth=min_depth,
+                               max_depth=max_depth, num_depth_candidates=num_depth_candidates, depth_from_argmax=depth_from_argmax,
+                               pred_bidir_depth=pred_bidir_depth)
 
-                # ---- matching layer
-                if task == 'depth':
-                    cand = self._depth_candidates(min_depth, max_depth, num_depth_candidates, dev)
-                    f0c, f1c = tok0, tok1
-                    if pred_bidir_depth:
-                        f0c, f1c = torch.cat([tok0, tok1], 0), torch.cat([tok1, tok0], 0)
-                    if hasattr(ops, 'depth_cam') and tok0.is_cuda:     # K / up, K^-1, (inverse) pose packed on the device, no sync
-                        cam = ops.depth_cam(intrinsics, pose, float(up), pred_bidir_depth)
-                    else:
-                        kc, pc = k_cur, pose
-                        if pred_bidir_depth:
-                            kc = k_cur.repeat(2, 1, 1)
-                            pc = torch.cat([pose, torch.inverse(pose)], 0)
-                        cam = torch.cat([torch.inverse(kc).flatten(1), pc[:, :3, :3].flatten(1), pc[:, :3, 3],
-                                         kc.flatten(1)], 1).float().contiguous()
-                    flow_pred = ops.depth_corr_softmax(f0c, f1c, h, w, cam, cand.contiguous(), depth_from_argmax)
+    def _encode(self, images, task='flow'):
+        """The encode step: the CNN encoder of the images of the tuple ``images``, stacked in that order -> per-scale feature maps
+        ``[N, C, h, w]``, low -> high resolution.  Strictly per image (InstanceNorm is per sample): a frame's features are the same
+        whichever pair asks for them."""
+        ops = self.ops
+        input_norm = None
+        if task == 'flow':                  # stereo / depth loaders normalise already (unimatch.py:122-124)
+            if self.backbone.takes_raw_images(ops, images[0]):
+                input_norm = (_IMAGENET_MEAN, _IMAGENET_STD)            # folded into the stem's image packing
+            else:
+                mean, std = self._constants(images[0].device)
+                images = tuple((im / 255. - mean) / std for im in images)
+        stack = images[0] if len(images) == 1 else torch.cat(images, 0)
+        return self.backbone(stack, ops, input_norm)[::-1]              # low -> high resolution
+
+    def _match(self, feats, nb, attn_type='', attn_splits_list=None, corr_radius_list=None, prop_radius_list=None, num_reg_refine=1,
+               pred_bidir_flow=False, task='flow', intrinsics=None, pose=None, min_depth=1. / 0.5, max_depth=1. / 10,
+               num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False):
+        """The match step: everything after the encoder, on per-scale features ``feats[s] = [f0; f1]`` (``[2 nb, C, h, w]``, the
+        first images of the ``nb`` pairs, then the second ones)."""
+        ops = self.ops
+        dev = feats[0].device
+        flow, pred = None, None
+        for s in range(self.num_scales):
+            m0, m1 = feats[s][:nb], feats[s][nb:]                         # [B, C, h, w]
+            both = None
+            if pred_bidir_flow and s > 0:
+                m0, m1 = torch.cat([m0, m1], 0), torch.cat([m1, m0], 0)
+                ori0, ori1 = _to_tokens(m0), _to_tokens(m1)               # pre-position, pre-warp tokens
+            else:
+                both = _to_tokens(feats[s])                               # the encoder's batched output is [f0; f1]
+                ori0, ori1 = both[:nb], both[nb:]
+            h, w = m0.shape[-2:]
+            up = self.upsample_factor * 2 ** (self.num_scales - 1 - s)
+            if task == 'depth':
+                k_cur = intrinsics.clone()
+                k_cur[:, :2] = k_cur[:, :2] / up
+            if s > 0:
+                if hasattr(ops, 'flow_upsample2x') and flow.is_cuda:
+                    flow = ops.flow_upsample2x(flow, 2.0)          # unimatch.py:162-163 on um_flow_upsample2x
                 else:
-                    radius = corr_radius_list[s]
-                    if radius == -1:
-                        if task == 'flow':
-                            flow_pred = ops.global_corr_softmax_flow(tok0, tok1, h, w, pred_bidir_flow)
-                        elif task == 'stereo':
-                            flow_pred = ops.global_corr_softmax_stereo(tok0, tok1, h, w)
-                        else:
-                            raise NotImplementedError
+                    flow = F.interpolate(flow, scale_factor=2, mode='bilinear', align_corners=True) * 2
+            tok1 = ori1
+            if flow is not None:
+                assert task != 'depth'
+                disp = torch.cat([-flow, torch.zeros_like(flow)], 1) if task == 'stereo' else flow
+                if hasattr(ops, 'flow_warp') and ori1.is_cuda:
+                    tok1 = ops.flow_warp(ori1, disp.contiguous(), h, w)
+                else:
+                    tok1 = _to_tokens(_warp(m1, disp))
+            splits, prop_r = attn_splits_list[s], prop_radius_list[s]
+            pos = self._position(h, w, splits, dev)
+            if self.debug_taps is not None:
+                self.debug_taps[f'backbone0_s{s}'], self.debug_taps[f'backbone1_s{s}'] = m0, m1
+            if tok1 is ori1 and both is not None:
+                # no warp, no bidirectional stacking: the stream [f0; f1] is the encoder's output -- one position add on
+                # the whole of it instead of two adds and a concatenation
+                tok0, tok1 = self.transformer(ops, None, None, h, w, attn_type, splits, stream=both + pos)
+            else:
+                tok0, tok1 = self.transformer(ops, ori0 + pos, tok1 + pos, h, w, attn_type, splits)
+            if self.debug_taps is not None:
+                self.debug_taps[f'f0_s{s}'], self.debug_taps[f'f1_s{s}'] = _to_map(tok0, h, w), _to_map(tok1, h, w)
+
+            # ---- matching layer
+            if task == 'depth':
+                cand = self._depth_candidates(min_depth, max_depth, num_depth_candidates, dev)
+                f0c, f1c = tok0, tok1
+                if pred_bidir_depth:
+                    f0c, f1c = torch.cat([tok0, tok1], 0), torch.cat([tok1, tok0], 0)
+                if hasattr(ops, 'depth_cam') and tok0.is_cuda:     # K / up, K^-1, (inverse) pose packed on the device, no sync
+                    cam = ops.depth_cam(intrinsics, pose, float(up), pred_bidir_depth)
+                else:
+                    kc, pc = k_cur, pose
+                    if pred_bidir_depth:
+                        kc = k_cur.repeat(2, 1, 1)
+                        pc = torch.cat([pose, torch.inverse(pose)], 0)
+                    cam = torch.cat([torch.inverse(kc).flatten(1), pc[:, :3, :3].flatten(1), pc[:, :3, 3],
+                                     kc.flatten(1)], 1).float().contiguous()
+                flow_pred = ops.depth_corr_softmax(f0c, f1c, h, w, cam, cand.contiguous(), depth_from_argmax)
+            else:
+                radius = corr_radius_list[s]
+                if radius == -1:
+                    if task == 'flow':
+                        flow_pred = ops.global_corr_softmax_flow(tok0, tok1, h, w, pred_bidir_flow)
+                    elif task == 'stereo':
+                        flow_pred = ops.global_corr_softmax_stereo(tok0, tok1, h, w)
                     else:
-                        if task not in ('flow', 'stereo'):
-                            raise NotImplementedError
-                        flow_pred = ops.local_corr_softmax(tok0, tok1, h, w, radius, one_d=(task == 'stereo'))
-                flow = flow_pred if flow is None else flow + flow_pred
+                        raise NotImplementedError
+                else:
+                    if task not in ('flow', 'stereo'):
+                        raise NotImplementedError
+                    flow_pred = ops.local_corr_softmax(tok0, tok1, h, w, radius, one_d=(task == 'stereo'))
+            flow = flow_pred if flow is None else flow + flow_pred
+            if task == 'stereo':
+                flow = flow.clamp(min=0)
+            if self.debug_taps is not None:
+                self.debug_taps[f'flow_match_s{s}'] = flow
+
+            # ---- propagation
+            if (pred_bidir_flow or pred_bidir_depth) and s == 0:
+                tok0 = torch.cat([tok0, tok1], 0)
+            flow = self.feature_flow_attn(ops, tok0, flow.contiguous(), h, w,
+                                          local_window_attn=prop_r > 0, local_window_radius=prop_r)
+            if self.debug_taps is not None:
+                self.debug_taps[f'flow_prop_s{s}'] = flow
+            if s < self.num_scales - 1:
+                continue
+
+            # ---- full-resolution prediction
+            f0_map = _to_map(tok0, h, w)
+            if not self.reg_refine:
+                if task == 'stereo':
+                    pad = torch.cat([-flow, torch.zeros_like(flow)], 1)
+                    pred = -self._upsample(pad, f0_map)[:, :1]
+                elif task == 'depth':
+                    pad = torch.cat([flow, torch.zeros_like(flow)], 1)
+                    pred = self._upsample(pad, f0_map, is_depth=True).clamp(min=min_depth, max=max_depth)[:, :1]
+                else:
+                    pred = self._upsample(flow, f0_map)
+                continue
+            assert num_reg_refine > 0
+            pose_r = pose
+            nhwc = None                                     # channels-last refinement block on the library's convolutions
+            if getattr(ops, 'fused_conv', False) and tok0.is_cuda:      # every task: flow_dim 2 (flow) / 1 (disparity, inverse depth)
+                nhwc = NhwcUpdateBlock(ops, self.refine, self.refine_proj)
+                nhwc.begin(tok0, tok0.shape[0], h, w, iterations=num_reg_refine)
+            else:
+                proj = self.refine_proj(f0_map)             # same every iteration (unimatch.py:315-320)
+                net0, inp = torch.tanh(proj[:, :128]), torch.relu(proj[:, 128:])
+            for it in range(num_reg_refine):
+                if task == 'stereo':
+                    disp = torch.cat([-flow, torch.zeros_like(flow)], 1)
+                elif task == 'depth':
+                    if pred_bidir_depth and it == 0:
+                        ori0, ori1 = torch.cat([ori0, ori1], 0), torch.cat([ori1, ori0], 0)
+                    if hasattr(ops, 'rigid_flow') and flow.is_cuda:     # geometry.py:99-195 on um_rigid_flow (cam from the matching layer)
+                        disp = ops.rigid_flow(flow, cam)
+                    else:
+                        if pred_bidir_depth and it == 0:
+                            k_cur = k_cur.repeat(2, 1, 1)
+                            pose_r = torch.cat([pose, torch.inverse(pose)], 0)
+                        disp = _rigid_flow(1. / flow.squeeze(1), k_cur, pose_r)
+                else:
+                    disp = flow
+                if nhwc is not None:
+                    up_mask, delta = nhwc.iterate(ori0, ori1, disp.contiguous(), flow, it == num_reg_refine - 1)
+                else:
+                    corr = ops.local_corr_with_flow(ori0, ori1, disp.contiguous(), h, w, 4)
+                    _, up_mask, delta = self.refine(net0, inp, corr, flow)
+                if task == 'depth':
+                    flow = (flow - delta).clamp(min=min_depth, max=max_depth)
+                else:
+                    flow = flow + delta
                 if task == 'stereo':
                     flow = flow.clamp(min=0)
                 if self.debug_taps is not None:
-                    self.debug_taps[f'flow_match_s{s}'] = flow
-
-                # ---- propagation
-                if (pred_bidir_flow or pred_bidir_depth) and s == 0:
-                    tok0 = torch.cat([tok0, tok1], 0)
-                flow = self.feature_flow_attn(ops, tok0, flow.contiguous(), h, w,
-                                              local_window_attn=prop_r > 0, local_window_radius=prop_r)
-                if self.debug_taps is not None:
-                    self.debug_taps[f'flow_prop_s{s}'] = flow
-                if s < self.num_scales - 1:
-                    continue
-
-                # ---- full-resolution prediction
-                f0_map = _to_map(tok0, h, w)
-                if not self.reg_refine:
-                    if task == 'stereo':
-                        pad = torch.cat([-flow, torch.zeros_like(flow)], 1)
-                        pred = -self._upsample(pad, f0_map)[:, :1]
-                    elif task == 'depth':
-                        pad = torch.cat([flow, torch.zeros_like(flow)], 1)
-                        pred = self._upsample(pad, f0_map, is_depth=True).clamp(min=min_depth, max=max_depth)[:, :1]
-                    else:
-                        pred = self._upsample(flow, f0_map)
-                    continue
-                assert num_reg_refine > 0
-                pose_r = pose
-                nhwc = None                                     # channels-last refinement block on the library's convolutions
-                if getattr(ops, 'fused_conv', False) and tok0.is_cuda:      # every task: flow_dim 2 (flow) / 1 (disparity, inverse depth)
-                    nhwc = NhwcUpdateBlock(ops, self.refine, self.refine_proj)
-                    nhwc.begin(tok0, tok0.shape[0], h, w, iterations=num_reg_refine)
-                else:
-                    proj = self.refine_proj(f0_map)             # same every iteration (unimatch.py:315-320)
-                    net0, inp = torch.tanh(proj[:, :128]), torch.relu(proj[:, 128:])
-                for it in range(num_reg_refine):
-                    if task == 'stereo':
-                        disp = torch.cat([-flow, torch.zeros_like(flow)], 1)
-                    elif task == 'depth':
-                        if pred_bidir_depth and it == 0:
-                            ori0, ori1 = torch.cat([ori0, ori1], 0), torch.cat([ori1, ori0], 0)
-                        if hasattr(ops, 'rigid_flow') and flow.is_cuda:     # geometry.py:99-195 on um_rigid_flow (cam from the matching layer)
-                            disp = ops.rigid_flow(flow, cam)
-                        else:
-                            if pred_bidir_depth and it == 0:
-                                k_cur = k_cur.repeat(2, 1, 1)
-                                pose_r = torch.cat([pose, torch.inverse(pose)], 0)
-                            disp = _rigid_flow(1. / flow.squeeze(1), k_cur, pose_r)
-                    else:
-                        disp = flow
-                    if nhwc is not None:
-                        up_mask, delta = nhwc.iterate(ori0, ori1, disp.contiguous(), flow, it == num_reg_refine - 1)
-                    else:
-                        corr = ops.local_corr_with_flow(ori0, ori1, disp.contiguous(), h, w, 4)
-                        _, up_mask, delta = self.refine(net0, inp, corr, flow)
+                    self.debug_taps[f'flow_it{it}'] = flow
+                if it == num_reg_refine - 1:
                     if task == 'depth':
-                        flow = (flow - delta).clamp(min=min_depth, max=max_depth)
+                        pad = torch.cat([flow, torch.zeros_like(flow)], 1)
+                        pred = self._upsample(pad, f0_map, is_depth=True).clamp(
+                            min=min_depth, max=max_depth)[:, :1]
+                    elif nhwc is not None:
+                        pred = ops.convex_upsample(flow, up_mask, self.upsample_factor, False, mask_nhwc=True)
                     else:
-                        flow = flow + delta
-                    if task == 'stereo':
-                        flow = flow.clamp(min=0)
-                    if self.debug_taps is not None:
-                        self.debug_taps[f'flow_it{it}'] = flow
-                    if it == num_reg_refine - 1:
-                        if task == 'depth':
-                            pad = torch.cat([flow, torch.zeros_like(flow)], 1)
-                            pred = self._upsample(pad, f0_map, is_depth=True).clamp(
-                                min=min_depth, max=max_depth)[:, :1]
-                        elif nhwc is not None:
-                            pred = ops.convex_upsample(flow, up_mask, self.upsample_factor, False, mask_nhwc=True)
-                        else:
-                            pred = self._convex(flow, up_mask)
-            if task == 'stereo':
-                pred = pred.squeeze(1)
-            if task == 'depth':
-                pred = 1. / pred.squeeze(1)
+                        pred = self._convex(flow, up_mask)
+        if task == 'stereo':
+            pred = pred.squeeze(1)
+        if task == 'depth':
+            pred = 1. / pred.squeeze(1)
         return {'flow_preds': [pred]}

@@ -448,6 +448,36 @@ class HipOps:
         _abi.check(code, 'um_flow_warp')
         return out
 
+    def fwd_bwd_occlusion(self, fwd, bwd, alpha=0.01, beta=0.5):
+        """``um_fwd_bwd_occlusion``: forward / backward occlusion masks ``[B, H, W]`` fp32 in {0, 1} of the flows ``fwd``, ``bwd``
+        ``[B, 2, H, W]`` (the reference's forward_backward_consistency_check in one launch)."""
+        if not (fwd.is_cuda and fwd.dtype == torch.float32 and fwd.dim() == 4 and fwd.shape[1] == 2
+                and bwd.shape == fwd.shape and bwd.dtype == torch.float32 and bwd.device == fwd.device):
+            raise ValueError(f'fwd_bwd_occlusion: expected two CUDA float32 [B, 2, H, W] flows of one shape, got '
+                             f'{tuple(fwd.shape)} {fwd.dtype} and {tuple(bwd.shape)} {bwd.dtype}')
+        fwd, bwd = fwd.contiguous(), bwd.contiguous()
+        b, _, h, w = fwd.shape
+        occ_f = torch.empty((b, h, w), dtype=torch.float32, device=fwd.device)
+        occ_b = torch.empty_like(occ_f)
+        code = self._launch('fwd_bwd_occlusion', lambda: self.lib.um_fwd_bwd_occlusion(
+            _ptr(fwd), _ptr(bwd), _ptr(occ_f), _ptr(occ_b), b, h, w, float(alpha), float(beta), _stream()))
+        _abi.check(code, 'um_fwd_bwd_occlusion')
+        return occ_f, occ_b
+
+    def flow_to_rgb(self, flow):
+        """``um_flow_to_rgb``: Middlebury colouring ``[B, H, W, 3]`` uint8 of ``flow [B, 2, H, W]``, each image normalised by its own
+        maximum (the reference's flow_to_image per image)."""
+        if not (flow.is_cuda and flow.dtype == torch.float32 and flow.dim() == 4 and flow.shape[1] == 2):
+            raise ValueError(f'flow_to_rgb: expected a CUDA float32 [B, 2, H, W] flow, got {tuple(flow.shape)} {flow.dtype}')
+        flow = flow.contiguous()
+        b, _, h, w = flow.shape
+        rgb = torch.empty((b, h, w, 3), dtype=torch.uint8, device=flow.device)
+        ws = self._ws(self.lib.um_flow_to_rgb_workspace_bytes(b, h, w), flow.device)
+        code = self._launch('flow_to_rgb', lambda: self.lib.um_flow_to_rgb(
+            _ptr(flow), _ptr(rgb), b, h, w, _ptr(ws), ws.numel(), _stream()))
+        _abi.check(code, 'um_flow_to_rgb')
+        return rgb
+
     def flow_upsample2x(self, flow, mult=2.0):
         """``mult * F.interpolate(flow, scale_factor=2, mode='bilinear', align_corners=True)`` (``um_flow_upsample2x``)."""
         if not (flow.is_cuda and flow.dtype == torch.float32 and flow.dim() == 4):

@@ -88,6 +88,7 @@ class PartRunner:
         return (n, tuple(img0.shape), str(img0.device), small, version)
 
     def run(self, model, n, img0, img1, kw):
+        """``model._forward_one`` of the ``n`` contiguous sample ranges of ``img0`` / ``img1``, joined: ``{'flow_preds': [...]}``."""
         batch = img0.shape[0]
         bidir = 2 if (kw.get('pred_bidir_flow') or kw.get('pred_bidir_depth')) else 1
 
@@ -98,37 +99,49 @@ class PartRunner:
                     pk[key] = shard_batch(pk[key], r, n)
             return shard_batch(img0, r, n), shard_batch(img1, r, n), pk
 
-        def one(r, a0, a1, pk):
+        def compute(r, ins):
+            a0, a1, pk = ins
+            return model._forward_one(a0, a1, **pk)['flow_preds']
+
+        return self.run_parts(model, n, batch, bidir, self._key(model, n, img0, kw), img0.device, part_inputs, compute)
+
+    def run_parts(self, model, n, batch, bidir, key, device, prepare, compute):
+        """The general form of :meth:`run`: part ``r`` of ``n`` (sample range ``shard_bounds(batch, r, n)``) is ``compute(r,
+        prepare(r))`` -> its list of predictions ``[bidir * b_r, ...]``.  ``prepare`` runs on the caller's stream before any side stream
+        is released (the parts' inputs), ``compute`` on the part's stream; ``key`` identifies the call for the first-call-sequential
+        rule.  The predictions are joined in the reference's [forward; backward] order."""
+        cuda = device.type == 'cuda'
+
+        def one(r, ins):
             # buffers a captured graph owns are keyed by (graph token, lane): the parts of one capture must not share arrival counters
             # or activation planes (HipOps._split_workspace)
-            ops = model.ops if img0.is_cuda else None
+            ops = model.ops if cuda else None
             if ops is not None and hasattr(ops, 'workspace_lane'):
                 ops.workspace_lane = r
             try:
-                return model._forward_one(a0, a1, **pk)['flow_preds']
+                return compute(r, ins)
             finally:
                 if ops is not None and hasattr(ops, 'workspace_lane'):
                     ops.workspace_lane = 0
 
-        key = self._key(model, n, img0, kw)
-        concurrent = img0.is_cuda and key in self._seen and self._backend is not None and self._backend == self._backend_state(model)
+        concurrent = cuda and key in self._seen and self._backend is not None and self._backend == self._backend_state(model)
         outs = []
         if not concurrent:
             for r in range(n):
-                outs.append(one(r, *part_inputs(r)))
+                outs.append(one(r, prepare(r)))
             self._seen.add(key)
         else:
-            dev = img0.device
+            dev = device
             cur = torch.cuda.current_stream(dev)
             side = _side_streams(dev, n - 1)
-            ins = [part_inputs(r) for r in range(n)]                # sliced on the caller's stream
+            ins = [prepare(r) for r in range(n)]                    # sliced on the caller's stream
             for s in side:
                 s.wait_stream(cur)                                  # (before part 0 is enqueued: the side parts depend on the inputs only)
             outs = [None] * n
             for r in range(1, n):
                 with torch.cuda.stream(side[r - 1]):
-                    outs[r] = one(r, *ins[r])
-            outs[0] = one(0, *ins[0])                               # part 0 on the caller's stream
+                    outs[r] = one(r, ins[r])
+            outs[0] = one(0, ins[0])                                # part 0 on the caller's stream
             for r in range(1, n):
                 cur.wait_stream(side[r - 1])
         self._backend = self._backend_state(model)

@@ -119,3 +119,26 @@ def synth_camera(batch, height, width):
     pose[:3, :3] = rot
     pose[:3, 3] = torch.tensor([0.12, -0.03, 0.05])
     return k[None].repeat(batch, 1, 1).contiguous(), pose[None].repeat(batch, 1, 1).contiguous()
+
+
+def synth_frames(frames, height, width, seed=2000, blur=5, step=(3, -2)):
+    """A seeded moving-texture sequence ``[T, 3, H, W]`` (0..255): crops of one box-blurred noise canvas that slide by ``step`` =
+    (dx, dy) pixels per frame, plus a second texture patch moving the other way (consecutive frames with real correspondences
+    and an occluding object)."""
+    g = torch.Generator(device='cpu')
+    g.manual_seed(seed)
+    dx, dy = step
+    pad_x, pad_y = abs(dx) * frames + 8, abs(dy) * frames + 8
+    canvas = torch.rand(1, 3, height + 2 * pad_y, width + 2 * pad_x, generator=g)
+    canvas = torch.nn.functional.avg_pool2d(canvas, blur, stride=1, padding=blur // 2)
+    canvas = (canvas - canvas.amin()) / (canvas.amax() - canvas.amin())
+    ph, pw = max(4, height // 4), max(4, width // 4)
+    patch = torch.nn.functional.avg_pool2d(torch.rand(1, 3, ph + 4, pw + 4, generator=g), 3, stride=1, padding=1)[..., 2:-2, 2:-2]
+    out = []
+    for t in range(frames):
+        y0, x0 = pad_y + t * dy, pad_x + t * dx
+        f = canvas[0, :, y0:y0 + height, x0:x0 + width].clone()
+        py, px = (height - ph) // 2, min(max(0, (width - pw) // 2 - t * dx), width - pw)
+        f[:, py:py + ph, px:px + pw] = patch[0]
+        out.append(f)
+    return (torch.stack(out, 0) * 255.0).contiguous()
