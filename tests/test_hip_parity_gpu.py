@@ -940,11 +940,11 @@ def test_nhwc_update_block_matches_module(ops, fd, hw):
     # the six activation plane buffers are allocated and zeroed once per geometry and owner (ops.cached_planes_buffer) and handed
     # out again by every begin(): nothing may be read that this forward has not written -- poison every row but the zero padding
     # row with fp16 NaNs (0xffff) and run the forward again
-    planes = {k: v for k, v in ops._split_ws.items() if isinstance(k[0], tuple) and k[0][2] == b * h * w}
-    assert {k[0][1] for k in planes} == {'G', 'C1', 'CF', 'FH', 'F1', 'CORR'}
+    planes = {k: v for k, v in ops.workspace_entries() if isinstance(k.kind, tuple) and k.geometry[0] == b * h * w}
+    assert {k.kind[1] for k in planes} == {'G', 'C1', 'CF', 'FH', 'F1', 'CORR'}
     def poison():
         for key, buf in planes.items():
-            _, _, rows, ld = key[0]
+            rows, ld = key.geometry
             buf.view(torch.int16).view(2, rows + 1, ld)[:, :rows].fill_(-1)
 
     poison()
@@ -961,7 +961,7 @@ def test_nhwc_update_block_matches_module(ops, fd, hw):
                      addend=hst.P['zr1'][:-1].contiguous())
     # explicit release of the cached activation planes (~590 MB per stream at config 4): gone from the cache, rebuilt on demand
     ops.release_cached_planes()
-    assert not [k for k in ops._split_ws if isinstance(k[0], tuple)]
+    assert not [k for k, _ in ops.workspace_entries() if isinstance(k.kind, tuple)]
     upd.begin(f0.to(DEV), b, h, w)
     mask4, delta4 = upd.iterate(ori0.to(DEV), ori1.to(DEV), disp.to(DEV).contiguous(), flow.to(DEV), True)
     assert torch.equal(delta4, delta) and torch.equal(mask4, mask)
@@ -1668,8 +1668,8 @@ def test_split_handoffs_repeat_under_uneven_load():
     lib.um_census_enable(0)
     assert census['ffn_hsplit'] == launches >= 200 and census['ffn_tile'] == 0, census
     torch.cuda.synchronize()
-    assert {k[0] for k in o._split_ws} == {'_ks_ws', '_ffn_ws'}
-    for key, buf in o._split_ws.items():
+    assert {k.kind for k, _ in o.workspace_entries()} == {'attn_ksplit', 'ffn_hsplit'}
+    for key, buf in o.workspace_entries():
         assert int(buf[:64].count_nonzero()) == 0, key                       # the flags every launch must leave zero (>= 16 of them)
 
 
@@ -1690,16 +1690,17 @@ def test_graph_capture_owns_its_split_workspaces():
     model, i0, i1, fk = _graph_case('gmflow_s1', 320, 448)        # config 1's size: key-split attention, hidden-split FFN
     eager = model(i0, i1, **fk)['flow_preds'][0]
     ops = model.ops
-    eager_keys = set(ops._split_ws)
-    assert eager_keys and all(isinstance(k[2], int) for k in eager_keys)     # keyed by stream
+    entries = lambda: {k for k, _ in ops.workspace_entries()}
+    eager_keys = entries()
+    assert eager_keys and all(isinstance(k.owner, int) for k in eager_keys)  # keyed by stream
     g1, g2 = GraphedUniMatch(model), GraphedUniMatch(model)
     a = g1(i0, i1, **fk)['flow_preds'][0]
     b = g2(i0, i1, **fk)['flow_preds'][0]
     assert torch.equal(a, eager) and torch.equal(b, eager)
-    assert set(ops._split_ws) == eager_keys and ops.workspace_owner is None  # nothing of the graphs is left in the shared cache
+    assert entries() == eager_keys and ops.workspace_scope() == (None, 0)   # nothing of the graphs is left in the shared cache
     w1, w2 = (next(iter(g._graphs.values()))['workspaces'] for g in (g1, g2))
-    assert w1 and w2 and {k[0] for k in w1} == {k[0] for k in eager_keys}
-    ptrs = [t.data_ptr() for ws in (w1, w2, ops._split_ws) for t in ws.values()]
+    assert w1 and w2 and {k.kind for k in w1} == {k.kind for k in eager_keys}
+    ptrs = [t.data_ptr() for ws in (w1, w2, dict(ops.workspace_entries())) for t in ws.values()]
     assert len(set(ptrs)) == len(ptrs)                                       # every graph and the eager path: separate counters
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()                        # replayed concurrently on two streams, repeatedly
     for _ in range(20):
@@ -1712,7 +1713,7 @@ def test_graph_capture_owns_its_split_workspaces():
         assert torch.equal(next(iter(g._graphs.values()))['out'], eager)
     for ws in (w1, w2):
         for key, buf in ws.items():
-            if isinstance(key[0], str):                                      # the counters (not the refinement's plane buffers)
+            if isinstance(key.kind, str):                                    # the counters (not the refinement's plane buffers)
                 assert int(buf[:64].count_nonzero()) == 0
     # first-time request inside a capture (a user's own torch.cuda.graph, no warm-up under an owner): a capture-private zeroed
     # buffer that is NOT cached -- no later launch can meet counters an aborted capture left behind (raising here
@@ -1721,11 +1722,11 @@ def test_graph_capture_owns_its_split_workspaces():
     graph = torch.cuda.CUDAGraph()
     x = rnd(900, 2240, 128).to(DEV)
     with torch.cuda.graph(graph):
-        ws = fresh._split_workspace('_ffn_ws', 1 << 20, x.device)
+        ws = fresh._split_workspace('ffn_hsplit', (x.shape[0], 1024), x.device)      # config 1's FFN: a hidden-split launch
         probe = ws[:64].clone()
     graph.replay()
     torch.cuda.synchronize()
-    assert int(probe.count_nonzero()) == 0 and not fresh.__dict__.get('_split_ws')
+    assert int(probe.count_nonzero()) == 0 and not fresh.workspace_entries()
     # a graph around a WRAPPER of the model (ShardedUniMatch at world size 1) finds the HipOps through it: its workspaces are
     # owned by the graph exactly as above, and the capture succeeds (no eager fallback)
     from unimatch_amd.dist import ShardedUniMatch
@@ -1733,7 +1734,7 @@ def test_graph_capture_owns_its_split_workspaces():
     c = g3(i0, i1, **fk)['flow_preds'][0]
     entry = next(iter(g3._graphs.values()))
     assert entry is not False and entry['workspaces'] and torch.equal(c, eager)
-    assert set(ops._split_ws) == eager_keys and ops.workspace_owner is None
+    assert entries() == eager_keys and ops.workspace_scope() == (None, 0)
 
 
 def test_graph_of_a_forward_with_concurrent_parts_owns_one_workspace_set_per_part():
@@ -1755,16 +1756,17 @@ def test_graph_of_a_forward_with_concurrent_parts_owns_one_workspace_set_per_par
             got = graphed(i0, i1, **fk)['flow_preds'][0]
             entry = next(iter(graphed._graphs.values()))
             assert entry is not False and torch.equal(got, eager)
-            lanes = {k[2][1] for k in entry['workspaces']}
+            lanes = {k.owner[1] for k in entry['workspaces']}
             assert lanes == {0, 1}, lanes
-            by_lane = {ln: {k[0]: t.data_ptr() for k, t in entry['workspaces'].items() if k[2][1] == ln} for ln in lanes}
+            by_lane = {ln: {(k.kind, k.geometry): t.data_ptr() for k, t in entry['workspaces'].items() if k.owner[1] == ln}
+                       for ln in lanes}
             assert set(by_lane[0]) == set(by_lane[1])
             assert all(by_lane[0][name] != by_lane[1][name] for name in by_lane[0])
             for _ in range(10):
                 again = graphed(i0, i1, **fk)['flow_preds'][0]
             torch.cuda.synchronize()
             assert torch.equal(again, eager)
-            assert model.ops.workspace_owner is None and model.ops.workspace_lane == 0
+            assert model.ops.workspace_scope() == (None, 0)
     finally:
         model.launch_parts = None
 
@@ -1794,7 +1796,47 @@ def test_small_launch_workspaces_survive_a_change_of_geometry():
     torch.cuda.synchronize()
     assert torch.isfinite(first).all() and torch.equal(first, torch.cat([two, one], 0))
     assert all(torch.equal(r, first) for r in again)
+    # two geometries whose workspaces have EQUAL byte counts but different plans -- attention: 32 query tiles in 4 key parts
+    # against 64 tiles in 2; FFN: 448 against 480 rows in 4 tiles -- get a buffer each, and alternating them stays bitwise
+    lib, ops = model.ops.lib, model.ops
+    cases = (('attn_ksplit', (1, 128, 992), (2, 128, 800), (2, 16, 124, 8, 62), (4, 16, 100, 8, 50)),
+             ('ffn_hsplit', (1, 64, 224), (1, 96, 160), (448, 1024), (480, 1024)))
+    for kind, img_a, img_b, geo_a, geo_b in cases:
+        size = lib.um_window_attn_ksplit_workspace_bytes if kind == 'attn_ksplit' else lib.um_ffn_split_workspace_bytes
+        assert size(*geo_a) == size(*geo_b) > 0
+        pa, pb = (tuple(t.to(DEV) for t in synth_images(*g, seed=14, kind='shift')) for g in (img_a, img_b))
+        ra, rb = (model(*p, **fk)['flow_preds'][0] for p in (pa, pb))
+        ra2, rb2 = (model(*p, **fk)['flow_preds'][0] for p in (pa, pb))
+        assert torch.isfinite(ra).all() and torch.isfinite(rb).all() and torch.equal(ra, ra2) and torch.equal(rb, rb2), kind
+        bufs = {k.geometry: buf for k, buf in ops.workspace_entries() if k.kind == kind}
+        assert bufs[geo_a].data_ptr() != bufs[geo_b].data_ptr(), kind
     model.check_operand_range()
+
+
+def test_a_part_that_raises_leaves_the_model_usable(monkeypatch):
+    """the concurrent fork / join is exception-safe.  With two parts forced, a side part that raises propagates its error,
+    leaves no workspace scope behind and the caller's stream joined with the side stream: the next plain call is bitwise the warm one."""
+    model, i0, i1, fk = _graph_case('gmflow_s1', 128, 192, batch=2)
+    model.launch_parts = 2
+    try:
+        warm = model(i0, i1, **fk)['flow_preds'][0]                  # sequential first call
+        caller, plain = torch.cuda.current_stream(), model._forward_one
+
+        def side_part_raises(*args, **kw):
+            if torch.cuda.current_stream() != caller:
+                raise ValueError('side part failed')
+            return plain(*args, **kw)
+
+        monkeypatch.setattr(model, '_forward_one', side_part_raises)
+        with pytest.raises(ValueError, match='side part failed'):
+            model(i0, i1, **fk)                                      # concurrent: part 1 is enqueued first, on the side stream
+        assert model.ops.workspace_scope() == (None, 0)
+        monkeypatch.undo()
+        again = model(i0, i1, **fk)['flow_preds'][0]
+    finally:
+        model.launch_parts = None
+    torch.cuda.synchronize()
+    assert torch.equal(again, warm)
 
 
 @pytest.mark.parametrize('name', ['gmflow_s1', 'gmflow_s2_rr6', 'gmstereo_s2_rr3'])

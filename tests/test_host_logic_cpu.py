@@ -333,6 +333,70 @@ def test_concurrent_wrapper_splits_and_reassembles_a_batch():
     assert ConcurrentUniMatch(model, parts=1)(i0, i1, **kw)['flow_preds'][0].shape == whole.shape
 
 
+def test_workspace_registry_keys_scopes_and_cap():
+    """The scratch registry behind ``HipOps`` (stream handle and capture state injected, CPU tensors): a buffer is found again only
+    for the same (kind, geometry, device, owner) -- equal byte counts of two geometries are two entries; the owner is the stream,
+    or (graph token, lane) inside ``graph_scope`` / ``part_scope``, which are thread-local and restore on exceptions; at most
+    ``GEOMETRIES`` split workspaces per (kind, device, owner), oldest evicted first, one plane geometry; a first request inside a
+    capture is private and never cached; ``release_cached_planes`` drops only the planes."""
+    import threading
+    from unimatch_amd.ops import WorkspaceKey, WorkspaceRegistry
+    stream, capturing = [7], [False]
+    reg = WorkspaceRegistry(stream=lambda: stream[0], capturing=lambda: capturing[0])
+    cpu = torch.device('cpu')
+    get = lambda kind, geo, nbytes=512, keep=reg.GEOMETRIES: reg._workspace(kind, geo, nbytes, cpu, keep)
+
+    a = get('attn_ksplit', (2, 40, 56, 20, 28))
+    b = get('attn_ksplit', (4, 40, 56, 20, 28))                   # same byte count, another geometry
+    assert a is not b and get('attn_ksplit', (2, 40, 56, 20, 28)) is a and int(a.count_nonzero()) == 0
+    stream[0] = 9
+    assert get('attn_ksplit', (2, 40, 56, 20, 28)) is not a       # another stream, another owner
+    assert {k.owner for k, _ in reg.workspace_entries()} == {7, 9}
+
+    inside, entered, leave = {}, threading.Event(), threading.Event()
+
+    def other_thread():
+        with reg.part_scope(1):
+            inside['scope'] = reg.workspace_scope()
+            entered.set()
+            leave.wait(10)
+    t = threading.Thread(target=other_thread)
+    t.start()
+    assert entered.wait(10) and reg.workspace_scope() == (None, 0)
+    leave.set()
+    t.join()
+    assert inside['scope'] == (None, 1)
+
+    token = object()
+    with pytest.raises(KeyError):
+        with reg.graph_scope(token) as owned:
+            with reg.part_scope(1):
+                assert reg.workspace_scope() == (token, 1)
+                lane1 = get('ffn_hsplit', (4480, 1024))
+                raise KeyError('capture failed')
+    assert reg.workspace_scope() == (None, 0)
+    assert owned == {WorkspaceKey('ffn_hsplit', (4480, 1024), cpu, (token, 1)): lane1}
+    assert not [k for k, _ in reg.workspace_entries() if k.kind == 'ffn_hsplit']      # the graph's buffers left the registry
+
+    for m in range(reg.GEOMETRIES + 2):
+        get('ffn_hsplit', (m, 1024))
+    kept = [k.geometry[0] for k, _ in reg.workspace_entries() if k.kind == 'ffn_hsplit']
+    assert kept == list(range(2, reg.GEOMETRIES + 2))
+    get(('planes', 'G'), (100, 512), keep=1)                       # (HipOps.cached_planes_buffer's rule: one geometry)
+    get(('planes', 'G'), (200, 512), keep=1)
+    assert [k.geometry for k, _ in reg.workspace_entries() if k.kind == ('planes', 'G')] == [(200, 512)]
+
+    capturing[0] = True
+    before = reg.workspace_entries()
+    private = get('attn_ksplit', (8, 40, 56, 20, 28))
+    assert int(private.count_nonzero()) == 0 and reg.workspace_entries() == before
+    assert get('attn_ksplit', (2, 40, 56, 20, 28)) is not None     # a cached buffer is handed out inside a capture too
+    capturing[0] = False
+    reg.release_cached_planes()
+    assert not [k for k, _ in reg.workspace_entries() if isinstance(k.kind, tuple)]
+    assert len(reg.workspace_entries()) == len(before) - 1
+
+
 def test_forward_parts_plan_is_a_pure_function_of_the_call():
     """``streams.forward_parts``: the five BASELINE configs at their own batch sizes -- two concurrent forwards for
     configs 2 - 5 (and config 4 as written), one for the single pair of config 1 and for batches whose halves no longer fill the chip

@@ -6,6 +6,7 @@ once and replayed: at small batch the step is launch-bound (about 10 us of host 
 regime of the reference's own evaluation protocol (batch 1).  ``GraphedUniMatch(model)`` behaves like the model;
 each distinct (shapes, keyword arguments) combination is captured on first use.
 """
+import contextlib
 import warnings
 
 import torch
@@ -21,12 +22,12 @@ def _freeze(v):
 
 def _find_ops(model):
     """The ``HipOps`` of a model, looked for through wrappers (``ShardedUniMatch(model)``, ``DistributedDataParallel`` ...: the
-    attributes ``model`` / ``module``), so that the owner token reaches the instance whose workspaces the capture bakes in."""
+    attributes ``model`` / ``module``), so that the capture's scope reaches the instance whose workspaces it bakes in."""
     seen = set()
     while model is not None and id(model) not in seen:
         seen.add(id(model))
         ops = getattr(model, 'ops', None)
-        if ops is not None and hasattr(ops, 'claim_workspaces'):
+        if ops is not None and hasattr(ops, 'graph_scope'):
             return ops
         model = getattr(model, 'model', None) or getattr(model, 'module', None)
     return None
@@ -43,15 +44,11 @@ class GraphedUniMatch(torch.nn.Module):
     def _capture(self, img0, img1, kw):
         static = {'img0': img0.clone(), 'img1': img1.clone(),
                   'kw': {k: (v.clone() if torch.is_tensor(v) else v) for k, v in kw.items()}}
-        # The split small-launch workspaces (arrival counters that must be zero between launches) are keyed by an owner token for
-        # the duration of warm-up + capture: the eager warm-up allocates and zeroes them OUTSIDE the capture, the capture bakes
-        # in the same addresses, and this graph then owns them alone (ops.claim_workspaces) -- two graphs replayed concurrently
-        # share no counter, and an aborted capture's buffers are dropped with the token instead of being reused.
+        # The scratch buffers the forward bakes in (split-launch arrival counters that must be zero between launches, activation
+        # planes) are allocated and zeroed by the eager warm-up OUTSIDE the capture under this graph's scope, and the graph then
+        # owns them alone: two graphs replayed concurrently share no counter, and an aborted capture's buffers are dropped.
         ops = _find_ops(self.model)
-        token = object()
-        if ops is not None and hasattr(ops, 'claim_workspaces'):
-            ops.workspace_owner = token
-        try:
+        with ops.graph_scope(object()) if ops is not None else contextlib.nullcontext({}) as owned:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):           # warm-up: position tables, weight planes, split workspaces
@@ -62,13 +59,8 @@ class GraphedUniMatch(torch.nn.Module):
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 static['out'] = self.model(static['img0'], static['img1'], **static['kw'])['flow_preds'][0]
-            static['graph'] = graph
-            if ops is not None and hasattr(ops, 'claim_workspaces'):
-                static['workspaces'] = ops.claim_workspaces(token)      # alive as long as the graph
-        finally:
-            if ops is not None and hasattr(ops, 'claim_workspaces'):
-                ops.workspace_owner = None
-                ops.claim_workspaces(token)                             # failure path: nobody may reuse what the capture touched
+        static['graph'] = graph
+        static['workspaces'] = owned                # alive as long as the graph
         return static
 
     def forward(self, img0, img1, **kw):

@@ -30,6 +30,8 @@ import torch.nn.functional as F
 from .encoder import CNNEncoder
 from .refine import BasicUpdateBlock, convex_upsample
 from .refine_nhwc import NhwcUpdateBlock
+from .dist import shard_batch, shard_bounds
+from .streams import PartRunner, forward_parts
 
 _IMAGENET_MEAN = (0.485, 0.456, 0.406)
 _IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -332,7 +334,7 @@ class UniMatch(nn.Module):
         self.debug_taps = None            # set to a dict to collect named intermediates (diagnostics only)
         self.check_weights = False        # True: fingerprint the parameters every forward (see _check_weight_print)
         self._weight_print = None
-        self._runner = None               # streams.PartRunner: the batch as concurrent forwards (see forward)
+        self._runner = PartRunner()       # the batch as concurrent forwards (see forward)
 
     # ------------------------------------------------------------------ hot-path backend
     def set_precision(self, precision):
@@ -466,6 +468,15 @@ class UniMatch(nn.Module):
         configuration) -- the batch as two forwards of contiguous sample ranges on two HIP streams, joined on the caller's
         stream.  The samples of a batch are independent (unimatch.py:113-367 has no cross-sample operation), every part is bitwise
         the plain forward of its samples."""
+        return self._forward_batch(img0, img1, self.launch_parts, attn_type, attn_splits_list, corr_radius_list, prop_radius_list,
+                                   num_reg_refine, pred_bidir_flow, task, intrinsics, pose, min_depth, max_depth, num_depth_candidates,
+                                   depth_from_argmax, pred_bidir_depth)
+
+    def _forward_batch(self, img0, img1, parts, attn_type=None, attn_splits_list=None, corr_radius_list=None,
+                       prop_radius_list=None, num_reg_refine=1, pred_bidir_flow=False, task='flow', intrinsics=None,
+                       pose=None, min_depth=1. / 0.5, max_depth=1. / 10, num_depth_candidates=64,
+                       depth_from_argmax=False, pred_bidir_depth=False, **kwargs):
+        """:meth:`forward` with ``parts`` in place of ``launch_parts`` (``ConcurrentUniMatch`` forces its own count here)."""
         if self.training:
             raise RuntimeError('this module implements inference only: call .eval() '
                                '(training-mode auxiliary outputs of the reference are out of scope)')
@@ -473,19 +484,30 @@ class UniMatch(nn.Module):
                   prop_radius_list=prop_radius_list, num_reg_refine=num_reg_refine, pred_bidir_flow=pred_bidir_flow, task=task,
                   intrinsics=intrinsics, pose=pose, min_depth=min_depth, max_depth=max_depth,
                   num_depth_candidates=num_depth_candidates, depth_from_argmax=depth_from_argmax, pred_bidir_depth=pred_bidir_depth)
-        parts = self.launch_parts
-        if parts is None:
-            parts = 1
-            if img0.is_cuda and self.debug_taps is None:
-                from .streams import forward_parts
-                parts = forward_parts(task, attn_type, self.num_scales, self.reg_refine, img0.shape[0], img0.shape[-2], img0.shape[-1])
-        parts = min(int(parts), img0.shape[0])
+        batch = img0.shape[0]
+        parts = self._plan_parts(parts, task, attn_type, batch, img0.shape[-2], img0.shape[-1], img0.is_cuda)
         if parts <= 1:
             return self._forward_one(img0, img1, **kw)
-        if self._runner is None:
-            from .streams import PartRunner
-            self._runner = PartRunner()
-        return self._runner.run(self, parts, img0, img1, kw)
+
+        def prepare(r):
+            pk = dict(kw, intrinsics=shard_batch(intrinsics, r, parts), pose=shard_batch(pose, r, parts))
+            return shard_batch(img0, r, parts), shard_batch(img1, r, parts), pk
+
+        def compute(r, ins):
+            a0, a1, pk = ins
+            return self._forward_one(a0, a1, **pk)['flow_preds']
+
+        bidir = 2 if (pred_bidir_flow or pred_bidir_depth) else 1
+        return self._runner.run_parts(self, parts, batch, bidir, img0.shape, img0.device, kw, prepare, compute)
+
+    def _plan_parts(self, parts, task, attn_type, batch, height, width, is_cuda):
+        """How many concurrent parts a call of ``batch`` samples runs as: ``parts`` when given (``launch_parts``), else
+        ``streams.forward_parts`` (one with ``debug_taps``: the taps are per forward), never more than the batch."""
+        if parts is None:
+            parts = 1
+            if is_cuda and self.debug_taps is None:
+                parts = forward_parts(task, attn_type, self.num_scales, self.reg_refine, batch, height, width)
+        return min(int(parts), batch)
 
     # ------------------------------------------------------------------ video: consecutive frames
     def _carry_state(self, frames):
@@ -603,21 +625,10 @@ class UniMatch(nn.Module):
 
         ref = chunk[-1][-1]
         h8, w8 = ref.shape[-2:]
-        parts = self.launch_parts
-        if parts is None:
-            parts = 1
-            if ref.is_cuda and self.debug_taps is None:
-                from .streams import forward_parts
-                parts = forward_parts('flow', kw['attn_type'], self.num_scales, self.reg_refine, nb,
-                                      self.upsample_factor * h8, self.upsample_factor * w8)
-        parts = min(int(parts), nb)
+        parts = self._plan_parts(self.launch_parts, 'flow', kw['attn_type'], nb, self.upsample_factor * h8, self.upsample_factor * w8,
+                                 ref.is_cuda)
         if parts <= 1:
             return self._match(stream(0, nb), nb, **kw)['flow_preds'][0]
-        if self._runner is None:
-            from .streams import PartRunner
-            self._runner = PartRunner()
-        from .dist import shard_bounds
-        bidir = 2 if kw['pred_bidir_flow'] else 1
 
         def prepare(r):
             lo, hi = shard_bounds(nb, r, parts)
@@ -626,9 +637,9 @@ class UniMatch(nn.Module):
         def compute(r, ins):
             return self._match(ins[0], ins[1], **kw)['flow_preds']
 
-        small = tuple(sorted((k, tuple(v) if isinstance(v, list) else v) for k, v in kw.items()))
-        key = ('sequence', parts, nb, tuple(ref.shape[1:]), str(ref.device), small, sum(p._version for p in self.parameters()))
-        return self._runner.run_parts(self, parts, nb, bidir, key, ref.device, prepare, compute)['flow_preds'][0]
+        bidir = 2 if kw['pred_bidir_flow'] else 1
+        return self._runner.run_parts(self, parts, nb, bidir, (nb,) + tuple(ref.shape[1:]), ref.device, kw, prepare,
+                                      compute)['flow_preds'][0]
 
     def _forward_one(self, img0, img1, attn_type=None, attn_splits_list=None, corr_radius_list=None,
                      prop_radius_list=None, num_reg_refine=1, pred_bidir_flow=False, task='flow', intrinsics=None,

@@ -5,8 +5,11 @@ shapes / dtypes / contiguity, allocates the output (and scratch workspace) as to
 the HIP kernels on torch's current stream through ``ctypes``.  Feature tensors are token-major
 ``[N, L, C]`` fp32 (C = 128); flow-like tensors are ``[N, V, h, w]`` fp32 as in the reference.
 """
+import contextlib
 import ctypes
+import threading
 import weakref
+from collections import namedtuple
 
 import torch
 
@@ -65,7 +68,80 @@ def pack_kv4_weights(weights):
     return torch.cat([w4[:256], cross], 1).contiguous()
 
 
-class HipOps:
+WorkspaceKey = namedtuple('WorkspaceKey', 'kind geometry device owner')
+
+
+class _Scope(threading.local):
+    token = None               # the graph being warmed up / captured on this thread (graph_scope)
+    lane = 0                   # the part of a batch being enqueued on this thread (part_scope)
+
+
+class WorkspaceRegistry:
+    """Scratch that a launch finds zeroed -- split small launches' partials + arrival counters, the refinement block's activation
+    planes -- one buffer per ``WorkspaceKey``: ``kind`` ``'attn_ksplit'`` / ``'ffn_hsplit'`` / ``('planes', tag)``, ``geometry`` the
+    arguments of its size query, ``owner`` the current stream (launches in flight on two streams share no counter) or, inside the
+    thread-local :meth:`graph_scope` / :meth:`part_scope`, ``(graph token, lane)``: the eager warm-up allocates and zeroes a graph's
+    buffers OUTSIDE the capture, every graph and every part of a captured forward has its own.  A request inside a capture with no
+    buffer of its key gets a capture-private zeroed one (a memset node of the graph) that is never cached.  ``stream`` and
+    ``capturing`` are injectable: the bookkeeping runs without a GPU."""
+
+    GEOMETRIES = 8             # split workspaces kept per (kind, device, owner), oldest dropped first
+
+    def __init__(self, stream=None, capturing=None):
+        self._entries = {}
+        self._scope = _Scope()
+        self._stream_handle = stream or _stream
+        self._capturing = capturing or torch.cuda.is_current_stream_capturing
+
+    @contextlib.contextmanager
+    def graph_scope(self, token):
+        """Requests inside are owned by ``token``; on exit, exceptions included, its buffers leave the registry into the yielded
+        dict, which the graph keeps alive (an aborted capture's are dropped with it)."""
+        prev, self._scope.token = self._scope.token, token
+        owned = {}
+        try:
+            yield owned
+        finally:
+            self._scope.token = prev
+            for k in [k for k in self._entries if isinstance(k.owner, tuple) and k.owner[0] is token]:
+                owned[k] = self._entries.pop(k)
+
+    @contextlib.contextmanager
+    def part_scope(self, lane):
+        prev, self._scope.lane = self._scope.lane, lane
+        try:
+            yield
+        finally:
+            self._scope.lane = prev
+
+    def workspace_scope(self):
+        return self._scope.token, self._scope.lane
+
+    def workspace_entries(self):
+        """``[(WorkspaceKey, buffer), ...]``: a read-only view for tests."""
+        return list(self._entries.items())
+
+    def _workspace(self, kind, geometry, nbytes, device, keep):
+        scope = self._scope
+        owner = self._stream_handle() if scope.token is None else (scope.token, scope.lane)
+        buf = self._entries.get((kind, geometry, device, owner))         # (a plain tuple hashes and compares as the key does)
+        if buf is None:
+            if self._capturing():
+                return torch.zeros(nbytes, dtype=torch.uint8, device=device)
+            group = [k for k in self._entries if (k.kind, k.device, k.owner) == (kind, device, owner)]
+            for k in group[:max(0, len(group) + 1 - keep)]:
+                del self._entries[k]
+            buf = self._entries[WorkspaceKey(kind, geometry, device, owner)] = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        return buf
+
+    def release_cached_planes(self):
+        """Drop every cached activation-plane buffer (~590 MB per stream at config 4; captured graphs keep their own).  Safe at any
+        time between forwards: the next forward allocates and zeroes a fresh set."""
+        for k in [k for k in self._entries if isinstance(k.kind, tuple)]:
+            del self._entries[k]
+
+
+class HipOps(WorkspaceRegistry):
     """The hot path on MI355X.  ``precision``: 'exact' (fp16 hi+lo split MFMA operands) or 'fast' (bf16)."""
 
     fused_tail = True          # Transformer-layer linears / LayerNorm / GELU / residual run on um_linear_fwd
@@ -91,6 +167,8 @@ class HipOps:
         self.timer = None                     # set to a KernelTimer() to time launches with HIP events
         self.nplanes = 2 if precision == 'exact' else 1
         self._wcache = {}                     # weight planes, keyed by the identity + version of the fp32 tensors
+        self.cache_generation = 0             # counts builds of shared cache entries (streams.PartRunner)
+        WorkspaceRegistry.__init__(self)
 
     # ------------------------------------------------------------------ helpers
     def _ws(self, nbytes, device):
@@ -142,8 +220,8 @@ class HipOps:
         """Forget every cached operand plane (call after editing weights in place through ``.data``) and every split
         workspace (a launch that was cut short -- aborted capture, device error -- may have left arrival counters non-zero)."""
         self._wcache.clear()
-        self.__dict__.pop('_split_ws', None)
-        self.cache_generation = getattr(self, 'cache_generation', 0) + 1
+        self._entries.clear()
+        self.cache_generation += 1
 
     def _cache_put(self, key, tensors, value):
         if len(self._wcache) > 256:
@@ -153,7 +231,7 @@ class HipOps:
         self._wcache[key] = (tuple(weakref.ref(t) for t in tensors), value)
         # counts the builds of shared (stream-independent) cache entries: ConcurrentUniMatch only runs its parts on separate streams
         # when the previous forward built none -- an entry is written on the stream that first needs it
-        self.cache_generation = getattr(self, 'cache_generation', 0) + 1
+        self.cache_generation += 1
         return value
 
     def weight_planes(self, weights):
@@ -239,7 +317,7 @@ class HipOps:
         if y.shape[0] != m:
             raise ValueError('ffn_ln: x and y must have the same number of rows')
         out = torch.empty((m, 128), dtype=torch.float32, device=x.device)
-        ws = self._split_workspace('_ffn_ws', self.lib.um_ffn_split_workspace_bytes(m, hid), x.device)
+        ws = self._split_workspace('ffn_hsplit', (m, hid), x.device)
         code = self._launch('ffn', lambda: self.lib.um_ffn_ws_fwd(
             _ptr(x), _ptr(y), _ptr(w1p), _ptr(w2p), m, hid, self.WSHIFT, _ptr(norm.weight), _ptr(norm.bias),
             float(norm.eps), _ptr(out), self.mode, _ptr(ws) if ws is not None else None, ws.numel() if ws is not None else 0,
@@ -263,7 +341,7 @@ class HipOps:
         wc = self.kv4_weight_planes(kv_weights)
         out = torch.empty((m, 128), dtype=torch.float32, device=x.device)
         kv = torch.empty(self.lib.um_planes_bytes(4 * m, 128, self.mode), dtype=torch.uint8, device=x.device)
-        ws = self._split_workspace('_ffn_ws', self.lib.um_ffn_split_workspace_bytes(m, hid), x.device)
+        ws = self._split_workspace('ffn_hsplit', (m, hid), x.device)
         code = self._launch('ffn', lambda: self.lib.um_ffn_kv_fwd(
             _ptr(x), _ptr(y), _ptr(w1p), _ptr(w2p), m, hid, self.WSHIFT, _ptr(norm.weight), _ptr(norm.bias),
             float(norm.eps), _ptr(out), _ptr(wc), _ptr(kv), self.mode, _ptr(ws) if ws is not None else None,
@@ -307,54 +385,12 @@ class HipOps:
         _abi.check(code, 'um_window_attn_merge_fwd')
         return out
 
-    def _ksplit_workspace(self, nbytes, device):
-        return self._split_workspace('_ks_ws', nbytes, device)
-
-    def _split_workspace(self, name, nbytes, device):
-        """Scratch of a split small launch (attention: key split, FFN: hidden split -- partial results + arrival counters): zero
-        at allocation, left zero by every launch; one buffer per kernel, device AND owner, grown on demand.  The owner is the
-        current stream (two launches in flight on different streams must not share the counters) -- or, while a
-        ``GraphedUniMatch`` warms up and captures, that graph's token (``workspace_owner``): the buffer is then allocated and
-        zeroed by the eager warm-up OUTSIDE the capture, the capture only bakes its address in, every graph has its own buffer
-        (two graphs replayed concurrently share no counter), and ``claim_workspaces`` hands it to the graph object -- an aborted
-        capture drops it, so a buffer a capture may have left with stale counters is never reused."""
-        if not nbytes:
-            return None
-        cache = self.__dict__.setdefault('_split_ws', {})
-        owner = self._owner()
-        key = (name, device, owner)
-        buf = cache.get(key)
-        # EXACT size (round 6): the arrival counters sit at the head of the buffer and their count is the launch's tile count -- a bigger
-        # buffer left by another geometry has that geometry's partial results where this launch's counters must be zero (found with a
-        # batch of 3 as parts of 2 + 1 pairs on one stream: non-finite results; the same happened to ANY sequence of two small-launch
-        # geometries through one HipOps).  A geometry change on a stream costs one zero-fill.
-        if buf is None or buf.numel() != nbytes:
-            if torch.cuda.is_current_stream_capturing():
-                # First request INSIDE a capture (a user's own torch.cuda.graph around the model, or a wrapper GraphedUniMatch could
-                # not install its owner token through): a capture-PRIVATE buffer -- allocated from the graph's pool, zeroed by a memset
-                # node that replays with the graph, referenced by this capture only and never cached, so no later launch can meet
-                # counters an aborted capture left behind.  (Round 4 raised here, which turned such captures into a permanent eager
-                # fallback.)
-                return torch.zeros(nbytes, dtype=torch.uint8, device=device)
-            buf = cache[key] = torch.zeros(nbytes, dtype=torch.uint8, device=device)
-        return buf
-
-    workspace_owner = None     # set by GraphedUniMatch around warm-up + capture (see _split_workspace)
-    workspace_lane = 0         # set by streams.PartRunner around each part's forward: the parts of a batch run on different streams
-
-    def _owner(self):
-        """Who owns the per-launch scratch requested now: the current stream, or -- under a graph's token -- (token, lane): a captured
-        forward that runs its batch as concurrent parts (UniMatch.forward, streams.PartRunner) has one set of arrival counters /
-        partial buffers / activation planes PER PART (round-5 ADVICE: keyed by the token alone, the two halves shared them on two streams)."""
-        if self.workspace_owner is not None:
-            return (self.workspace_owner, self.workspace_lane)
-        return _stream()
-
-    def claim_workspaces(self, owner):
-        """Remove and return every split workspace allocated under ``owner`` (the graph keeps them alive; nobody else can get them)."""
-        cache = self.__dict__.setdefault('_split_ws', {})
-        mine = {k: cache.pop(k) for k in [k for k in cache if isinstance(k[2], tuple) and k[2][0] is owner]}
-        return mine
+    def _split_workspace(self, kind, geometry, device):
+        """Scratch of a split small launch, ``None`` when the launch is not split.  One buffer per geometry: the arrival counters sit
+        at its head, one per tile, where a buffer of another geometry holds partial results."""
+        size = self.lib.um_window_attn_ksplit_workspace_bytes if kind == 'attn_ksplit' else self.lib.um_ffn_split_workspace_bytes
+        nbytes = size(*geometry)
+        return self._workspace(kind, geometry, nbytes, device, self.GEOMETRIES) if nbytes else None
 
     def window_attention_qproj_merge(self, x, q_weight, k, v, streams, h, w, win_h, win_w, shift_h, shift_w, kv_rotate,
                                      merge_weight, norm, residual=None):
@@ -377,7 +413,7 @@ class HipOps:
             self._check_rows('residual', residual, 128)
         out = torch.empty((streams, h * w, 128), dtype=torch.float32, device=x.device)
         meta = {'flops': 4.0 * streams * h * w * win_h * win_w * 128}
-        ks = self._ksplit_workspace(self.lib.um_window_attn_ksplit_workspace_bytes(streams, h, w, win_h, win_w), x.device)
+        ks = self._split_workspace('attn_ksplit', (streams, h, w, win_h, win_w), x.device)
         code = self._launch('window_attn', lambda: self.lib.um_window_attn_qproj_merge_fwd(
             _ptr(x), _ptr(wqp), _ptr(kt) + 2 * koff, _ptr(vt) + 2 * voff, _ptr(wp), _ptr(norm.weight), _ptr(norm.bias),
             _ptr(residual) if residual is not None else None, float(norm.eps), self.WSHIFT, _ptr(out), streams, h, w, 128,
@@ -595,28 +631,10 @@ class HipOps:
         return torch.zeros(2 * (rows + 1) * ld * 2, dtype=torch.uint8, device='cuda')
 
     def cached_planes_buffer(self, tag, rows, ld, device):
-        """A ``planes_buffer(rows, ld)`` that is allocated and zeroed ONCE per (tag, geometry, device, owner) and handed out again on
-        later forwards (the refinement block's six activation buffers are 590 MB of zero-fill per forward at config 4 otherwise).
-        Only the padding row has to be zero and no kernel ever writes it; every other row is written before it is read.  Ownership
-        as for the split workspaces (:meth:`_split_workspace`): per stream, or per captured graph."""
-        name = ('planes', tag, rows, ld)
-        cache = self.__dict__.setdefault('_split_ws', {})
-        owner = self._owner()
-        device = torch.device(device)
-        for k in [k for k in cache if isinstance(k[0], tuple) and k[0][:2] == name[:2] and k[0] != name and k[2] == owner
-                  and torch.device(k[1]) == device]:
-            del cache[k]                       # one geometry per (owner, device) stays resident (a new input size replaces the old set)
-        if (name, device, owner) not in cache and torch.cuda.is_current_stream_capturing():
-            return self.planes_buffer(rows, ld)  # captured without a warm-up under an owner: the graph's own zero-filled buffer
-        return self._split_workspace(name, 2 * (rows + 1) * ld * 2, device)
-
-    def release_cached_planes(self):
-        """Drop every cached activation-plane buffer of this instance (the refinement block keeps ~590 MB per stream at config 4
-        alive between forwards; captured graphs keep their own sets until the graph object dies).  Safe at any time between
-        forwards: the next forward allocates and zeroes a fresh set."""
-        cache = self.__dict__.setdefault('_split_ws', {})
-        for k in [k for k in cache if isinstance(k[0], tuple) and k[0][0] == 'planes']:
-            del cache[k]
+        """A ``planes_buffer(rows, ld)`` allocated and zeroed once per (tag, geometry, device, owner) and handed out again (590 MB of
+        zero-fill per forward at config 4 otherwise): only the padding row has to be zero and no kernel writes it.  One geometry per
+        (tag, device, owner) stays resident."""
+        return self._workspace(('planes', tag), (rows, ld), 2 * (rows + 1) * ld * 2, torch.device(device), 1)
 
     def conv_weight_planes_from(self, weight):
         """Uncached: planes of ``weight [cout, cin, kh, kw]`` permuted to ``[cout, kh*kw*cin]`` -> ``(planes, cout, cin, kh, kw)``."""

@@ -14,7 +14,7 @@ fp32 noise floor the parity tables are measured against, and are bitwise those o
 """
 import torch
 
-from .dist import shard_batch, shard_bounds
+from .dist import shard_bounds
 
 
 def forward_parts(task, attn_type, num_scales, reg_refine, batch, height, width):
@@ -62,7 +62,7 @@ def _side_streams(dev, count):
 
 
 class PartRunner:
-    """Runs ``model._forward_one`` on ``n`` contiguous sample ranges -- part 0 on the caller's stream, the others on the process-wide
+    """Runs a batch as ``n`` parts of contiguous sample ranges -- part 0 on the caller's stream, the others on the process-wide
     side streams of the device -- joined on the caller's stream.
 
     The first forward of a geometry / argument set / parameter version runs the parts one after the other on the caller's stream:
@@ -70,6 +70,8 @@ class PartRunner:
     forward are kept per stream) -- concurrent first use would race on them.  The same after anything that makes the backend rebuild
     shared entries (``set_precision``, ``invalidate_weights``, a weight edited in place): the parts only go to separate streams when the
     backend object is the one of the previous forward and that forward built no shared cache entry (``HipOps.cache_generation``)."""
+
+    SEEN = 64                                    # first-call keys remembered; a forgotten one costs one sequential first call
 
     def __init__(self):
         self._seen = set()
@@ -81,69 +83,49 @@ class PartRunner:
         return (id(ops), getattr(ops, 'cache_generation', None))
 
     @staticmethod
-    def _key(model, n, img0, kw):
+    def _key(model, n, geometry, device, kw):
         version = sum(p._version for p in model.parameters())
         small = tuple(sorted((k, v if isinstance(v, (int, float, bool, str, type(None))) else
                               tuple(v) if isinstance(v, (list, tuple)) else tuple(v.shape)) for k, v in kw.items()))
-        return (n, tuple(img0.shape), str(img0.device), small, version)
+        return (n, tuple(geometry), str(device), small, version)
 
-    def run(self, model, n, img0, img1, kw):
-        """``model._forward_one`` of the ``n`` contiguous sample ranges of ``img0`` / ``img1``, joined: ``{'flow_preds': [...]}``."""
-        batch = img0.shape[0]
-        bidir = 2 if (kw.get('pred_bidir_flow') or kw.get('pred_bidir_depth')) else 1
-
-        def part_inputs(r):
-            pk = dict(kw)
-            for key in ('intrinsics', 'pose'):
-                if pk.get(key) is not None:
-                    pk[key] = shard_batch(pk[key], r, n)
-            return shard_batch(img0, r, n), shard_batch(img1, r, n), pk
-
-        def compute(r, ins):
-            a0, a1, pk = ins
-            return model._forward_one(a0, a1, **pk)['flow_preds']
-
-        return self.run_parts(model, n, batch, bidir, self._key(model, n, img0, kw), img0.device, part_inputs, compute)
-
-    def run_parts(self, model, n, batch, bidir, key, device, prepare, compute):
-        """The general form of :meth:`run`: part ``r`` of ``n`` (sample range ``shard_bounds(batch, r, n)``) is ``compute(r,
-        prepare(r))`` -> its list of predictions ``[bidir * b_r, ...]``.  ``prepare`` runs on the caller's stream before any side stream
-        is released (the parts' inputs), ``compute`` on the part's stream; ``key`` identifies the call for the first-call-sequential
-        rule.  The predictions are joined in the reference's [forward; backward] order."""
+    def run_parts(self, model, n, batch, bidir, geometry, device, kw, prepare, compute):
+        """Part ``r`` of ``n`` (sample range ``shard_bounds(batch, r, n)``) is ``compute(r, prepare(r))`` -> its list of predictions
+        ``[bidir * b_r, ...]``.  ``prepare`` runs on the caller's stream before any side stream is released (the parts' inputs),
+        ``compute`` on the part's stream, inside the backend's ``part_scope(r)``; ``geometry``, ``device`` and the keyword arguments
+        ``kw`` identify the call for the first-call-sequential rule.  The predictions are joined in the reference's [forward;
+        backward] order."""
         cuda = device.type == 'cuda'
 
         def one(r, ins):
-            # buffers a captured graph owns are keyed by (graph token, lane): the parts of one capture must not share arrival counters
-            # or activation planes (HipOps._split_workspace)
-            ops = model.ops if cuda else None
-            if ops is not None and hasattr(ops, 'workspace_lane'):
-                ops.workspace_lane = r
-            try:
+            if not cuda:
                 return compute(r, ins)
-            finally:
-                if ops is not None and hasattr(ops, 'workspace_lane'):
-                    ops.workspace_lane = 0
+            with model.ops.part_scope(r):                           # a captured graph owns one set of scratch per part
+                return compute(r, ins)
 
+        key = self._key(model, n, geometry, device, kw)
         concurrent = cuda and key in self._seen and self._backend is not None and self._backend == self._backend_state(model)
-        outs = []
         if not concurrent:
-            for r in range(n):
-                outs.append(one(r, prepare(r)))
+            outs = [one(r, prepare(r)) for r in range(n)]
+            if len(self._seen) >= self.SEEN:
+                self._seen.clear()
             self._seen.add(key)
         else:
-            dev = device
-            cur = torch.cuda.current_stream(dev)
-            side = _side_streams(dev, n - 1)
+            cur = torch.cuda.current_stream(device)
+            side = _side_streams(device, n - 1)
             ins = [prepare(r) for r in range(n)]                    # sliced on the caller's stream
             for s in side:
                 s.wait_stream(cur)                                  # (before part 0 is enqueued: the side parts depend on the inputs only)
             outs = [None] * n
-            for r in range(1, n):
-                with torch.cuda.stream(side[r - 1]):
-                    outs[r] = one(r, ins[r])
-            outs[0] = one(0, ins[0])                                # part 0 on the caller's stream
-            for r in range(1, n):
-                cur.wait_stream(side[r - 1])
+            try:
+                for r in range(1, n):
+                    with torch.cuda.stream(side[r - 1]):
+                        outs[r] = one(r, ins[r])
+                outs[0] = one(0, ins[0])                            # part 0 on the caller's stream
+            finally:
+                # also when a part raised: the side streams may still read the caller's inputs
+                for s in side:
+                    cur.wait_stream(s)
         self._backend = self._backend_state(model)
         # every prediction of the list: [bidir * b_r, ...] per part -> [bidir * batch, ...] in the reference's [forward; backward] order
         counts = [shard_bounds(batch, r, n)[1] - shard_bounds(batch, r, n)[0] for r in range(n)]
@@ -182,13 +164,7 @@ class ConcurrentUniMatch(torch.nn.Module):
 
     @property
     def _backend(self):
-        runner = getattr(self.model, '_runner', None)
-        return None if runner is None else runner._backend
+        return self.model._runner._backend
 
     def forward(self, img0, img1, **kw):
-        prev = self.model.launch_parts
-        self.model.launch_parts = self.parts
-        try:
-            return self.model(img0, img1, **kw)
-        finally:
-            self.model.launch_parts = prev
+        return self.model._forward_batch(img0, img1, self.parts, **kw)
