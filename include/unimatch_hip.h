@@ -113,7 +113,8 @@ int um_range_flags(unsigned* flags_out, int reset);
 #define UM_V_CONV_ROWS 11     /* conv_rows_kernel (row window shared by the horizontal taps)                            */
 #define UM_V_CONV_GENERIC 12  /* conv_kernel (tap-by-tap implicit GEMM)                                                 */
 #define UM_V_WATTN_W8 13      /* reserved: an 8-wave attention variant measured and dropped in round 5 (never counted) */
-#define UM_V_COUNT 14
+#define UM_V_CONV_PATCH_NORM 14 /* conv_patch_norm_kernel: the patch kernel normalising on load (ALSO counted as UM_V_CONV_PATCH) */
+#define UM_V_COUNT 15
 int um_census_enable(int on);
 long um_census_count(int variant);
 /* Key-tile census of the window attention (round 6; diagnostic, off by default).  In a window that carries the shifted-window mask
@@ -354,6 +355,23 @@ size_t um_nhwc_norm_workspace_bytes(int batch, int pixels, int channels);
 int um_nhwc_instance_norm(const float* x, const float* shortcut, const void* shortcut_planes, void* planes_out, float* f32_out,
                           int batch, int pixels, int channels, float eps, int normalize, int relu, const float* conv_stats,
                           int conv_stats_parts, void* workspace, size_t workspace_bytes, int mode, void* stream);
+
+/* The statistics step of um_nhwc_instance_norm on its own: per-part statistics of a convolution's epilogue (conv_stats,
+ * conv_stats_parts = um_conv_stats_parts() of that convolution) -> stats_out fp32 [batch][2][channels] = (mean, 1 / sqrt(var + eps)),
+ * the same kernel and the same bits um_nhwc_instance_norm(conv_stats) computes internally. */
+int um_nhwc_stats_finalize(const float* conv_stats, int conv_stats_parts, float* stats_out, int batch, int pixels, int channels,
+                           float eps, void* stream);
+/* Normalise on load: um_conv2d_fwd whose input is not operand planes but the PRODUCING convolution's fp32 output
+ * x [batch*hi*wi][cin] (16-byte aligned) and its statistics norm_stats [batch][2][cin] (um_nhwc_stats_finalize); the patch kernel
+ * computes relu?((x - mean) * rstd) and the hi | lo split while it stages the operand, in um_nhwc_instance_norm's arithmetic:
+ * output and stats_out are bit-identical to um_nhwc_instance_norm(planes_out) -> um_conv2d_fwd, without the normalisation's pass
+ * over memory (the middle InstanceNorm of a residual block, unimatch/backbone.py:27-31).  `relu`: on the output, as um_conv2d_fwd.
+ * Served for the geometries um_conv2d_norm_supported() returns 1 for (3x3 / stride 1 / pad 1 maps the 2-D patch kernel takes, at
+ * the tile widths where the path measured faster) -- a pure function of its arguments; any other geometry is an error (-2). */
+int um_conv2d_norm_supported(int hi, int wi, int cin, int cout, int kh, int kw, int stride, int pad_h, int pad_w, int mode);
+int um_conv2d_norm_fwd(const float* x, const float* norm_stats, int norm_relu, const void* w_planes, const float* bias, float* out,
+                       float* stats_out, int batch, int hi, int wi, int cin, int cout, int kh, int kw, int stride, int pad_h,
+                       int pad_w, int relu, int wshift, int mode, void* stream);
 
 /* Channels-last element-wise helpers of the refinement block (SepConvGRU, unimatch/reg_refine.py:55-76); every result is
  * written as operand planes into columns [coff, coff + channels) of a buffer [NS = 2][plane_rows][ld]:

@@ -1,7 +1,7 @@
 """Micro-benchmark of the HIP entry points at BASELINE sizes (GPU box).  Kernel time comes from the library's
 own hipEvents (um_timing_*), so split/convert pre-passes are reported separately from the main kernels.
 
-    python tools/bench_ops.py [attn] [gsv] [local] [linear] [conv] [--iters N] [--precision exact|fast] [--quick]
+    python tools/bench_ops.py [attn] [gsv] [local] [linear] [conv] [normconv] [--iters N] [--precision exact|fast] [--quick]
 """
 import ctypes
 import os
@@ -60,7 +60,7 @@ def main():
     args = sys.argv[1:]
     iters = int(args[args.index('--iters') + 1]) if '--iters' in args else 10
     prec = args[args.index('--precision') + 1] if '--precision' in args else 'exact'
-    what = [a for a in args if a in ('attn', 'gsv', 'local', 'linear', 'conv')] or ['attn', 'gsv', 'local', 'linear', 'conv']
+    what = [a for a in args if a in ('attn', 'gsv', 'local', 'linear', 'conv', 'normconv')] or ['attn', 'gsv', 'local', 'linear', 'conv']
     ops = HipOps(prec)
     lib = _abi.load()
     issued = 3.0 if prec == 'exact' else 1.0
@@ -130,6 +130,47 @@ def main():
             torch.cuda.synchronize()
             ms = (time.perf_counter() - t0) / iters * 1e3
             print(f'     MIOpen fp32 same conv                       {ms:8.4f} ms     {fl / ms / 1e9:8.1f} TF/s', flush=True)
+    if 'normconv' in what:
+        # a residual block's middle InstanceNorm + ReLU and its second convolution at config 2 (16 images), per tile width of the patch
+        # kernel: normalisation pass + convolution on planes against finalize + normalise-on-load convolution (kernel time per call
+        # from the library's own events; this table decides kNormOnLoad in conv.hip)
+        for (c, hh, ww, tag) in ((64, 256, 384, 'layer1 64 @256x384 (NT 2)'), (96, 128, 192, 'layer2 96 @128x192 (NT 3)'),
+                                 (128, 64, 96, 'layer3 128 @64x96 (NT 4)')):
+            nb = 16
+            xin = torch.randn(nb, c, hh, ww, device=dev, generator=g)
+            w1, w2 = (torch.randn(c, c, 3, 3, device=dev, generator=g) * 0.05 for _ in range(2))
+            planes, _ = ops.nchw_to_nhwc(xin, want_planes=True, want_f32=False)
+            t, _, _ = ops.conv2d_nhwc((planes, nb, hh, ww, c), w1, None, 1, (1, 1), stats=True)
+            st = ops.last_conv_stats
+            del planes, xin
+
+            def via_planes():
+                tp, _ = ops.nhwc_norm(t, nb, hh * ww, relu=True, want_planes=True, conv_stats=st)
+                return ops.conv2d_nhwc((tp, nb, hh, ww, c), w2, None, 1, (1, 1), stats=True)[0]
+
+            def on_load():
+                return ops.conv2d_nhwc_normed(t, st, (nb, hh, ww, c), w2, stats=True)[0]
+
+            res = {}
+            for name, fn in (('planes', via_planes), ('on load', on_load), ('planes', via_planes), ('on load', on_load)):
+                if name == 'on load' and not ops.conv2d_norm_supported(hh, ww, c, w2):
+                    continue
+                for _ in range(2):
+                    out = fn()
+                torch.cuda.synchronize()
+                lib.um_timing_enable(-1)
+                collect(lib)
+                for _ in range(iters):
+                    fn()
+                torch.cuda.synchronize()
+                lib.um_timing_enable(0)
+                tm = collect(lib)
+                norm_ms = tm['instance_norm'][0] * tm['instance_norm'][1] / iters
+                conv_ms = tm['conv'][0] * tm['conv'][1] / iters
+                res.setdefault(name, out)
+                print(f'normconv {tag:28s} {name:8s} norm {norm_ms:7.4f} ms + conv {conv_ms:7.4f} ms = {norm_ms + conv_ms:7.4f} ms', flush=True)
+            if len(res) == 2:
+                print(f'         bitwise equal: {torch.equal(res["planes"], res["on load"])}', flush=True)
     if 'conv' in what:
         # refinement-block convolutions at config 4 (4 pairs @ 1/4 resolution = 128 x 192)
         nb, hh, ww = 4, 128, 192

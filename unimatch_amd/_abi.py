@@ -14,7 +14,7 @@ MODE_FAST = 1
 
 # launch census ids (UM_V_* of the header): which kernel instantiation served a call
 CENSUS = {'wattn_tile': 0, 'wattn_ksplit': 1, 'ffn_tile': 2, 'ffn_hsplit': 3, 'gsv4': 4, 'gsv3': 5, 'k4_mfma': 6, 'k4_valu': 7,
-          'k3_mfma': 8, 'k3_valu': 9, 'conv_patch': 10, 'conv_rows': 11, 'conv_generic': 12, 'wattn_w8': 13}
+          'k3_mfma': 8, 'k3_valu': 9, 'conv_patch': 10, 'conv_rows': 11, 'conv_generic': 12, 'wattn_w8': 13, 'conv_patch_norm': 14}
 
 _c_int, _c_size_t, _c_void_p = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p
 
@@ -55,6 +55,9 @@ SIGNATURES = {
                                    _c_void_p, _c_int, _c_void_p, _c_int, _c_int, ctypes.c_long] + [_c_int] * 11 + [_c_void_p]),
     'um_conv2d_gru_add_fwd': (_c_int, [_c_int, _c_void_p, _c_int, _c_int, ctypes.c_long, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p,
                                         _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, ctypes.c_long] + [_c_int] * 11 + [_c_void_p]),
+    'um_conv2d_norm_supported': (_c_int, [_c_int] * 10),
+    'um_conv2d_norm_fwd': (_c_int, [_c_void_p, _c_void_p, _c_int] + [_c_void_p] * 4 + [_c_int] * 13 + [_c_void_p]),
+    'um_nhwc_stats_finalize': (_c_int, [_c_void_p, _c_int, _c_void_p] + [_c_int] * 3 + [ctypes.c_float, _c_void_p]),
     'um_conv_stats_bytes': (_c_size_t, [_c_int] * 3),
     'um_conv_stats_parts': (_c_int, [_c_int] * 8),
     'um_stem_planes_bytes': (_c_size_t, [_c_int] * 3),

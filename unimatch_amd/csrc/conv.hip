@@ -68,6 +68,11 @@ struct ConvArgs {
     int M;                        // B * Ho * Wo
     float out_scale;              // 2^-wshift
     int xcd;                      // XCD-aware workgroup order (0: plain; A/B switch UM_CONV_NO_XCD)
+    // normalise-on-load operand path of the patch kernel (conv_patch_norm_kernel): the producer's fp32 NHWC tensor [B*Hi*Wi][Cin]
+    // and its finalized InstanceNorm statistics [B][2][Cin] (mean, rstd) stand in for the operand planes `ap`
+    const float* xf;
+    const float* nstats;
+    int norm_relu;
 };
 
 __device__ __forceinline__ void conv_dma16(const void* base, unsigned byte_off, const unsigned char* lds_dst) {
@@ -715,12 +720,22 @@ struct ConvPatchLds {
     static constexpr int TOTAL = (STAGES > EPI + SCRATCH) ? STAGES : EPI + SCRATCH;   // tile, inside the then idle staging area:
 };                                                                // NT = 3 is exactly 80 KB, two workgroups fill the CU's LDS
 
-template <typename T, int NS, int NT>
-__global__ __launch_bounds__(512, (NT < 4 ? 2 : 1)) void conv_patch_kernel(ConvArgs a) {
+//
+// NORM = the normalise-on-load operand path (conv_patch_norm_kernel): the input is the producing convolution's fp32 output and its
+// InstanceNorm statistics, and the lanes that issue the patch DMA above instead load their 8 fp32 channels, compute
+// relu((x - mean) * rstd) and its hi | lo split in nhwc_apply_kernel's arithmetic (same operations, same order: the operands are
+// bit-for-bit the planes that kernel writes) and store them where the DMA would have put them.  The normalisation pass between two
+// convolutions, its read and its write, disappear; out-of-image patch pixels are zeroed AFTER the normalisation (norm(0) != 0).
+// The loads of chunk cc + 1 are issued in stage (cc, 0) and converted in stage (cc, 1); the second item of waves 0..2 follows one
+// stage later, so a lane holds one item (8 registers) across a stage.  The chunk's 16 means + 16 rstds arrive by scalar loads
+// (constant address space: written by an earlier kernel) and each lane selects its 8-channel half: no LDS (NT = 3 has none left).
+typedef const __attribute__((address_space(4))) float* um_const_f32p;
+
+template <typename T, int NS, int NT, bool NORM>
+__device__ __forceinline__ void conv_patch_body(const ConvArgs& a, unsigned char* lds) {
     using L = ConvPatchLds<NS, NT>;
     constexpr int ATILE = L::ATILE, WTILE = L::WTILE, ASLOT = L::ASLOT, WSLOT = L::WSLOT, WBASE = L::WBASE;
     constexpr int PW = L::PW;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -745,8 +760,12 @@ __global__ __launch_bounds__(512, (NT < 4 ? 2 : 1)) void conv_patch_kernel(ConvA
         const int py = j / PW, px = j - py * PW;
         const int iy = y0 - 1 + py, ix = x0 - 1 + px;
         const bool ok = j < L::PPIX && (unsigned)iy < (unsigned)a.Hi && (unsigned)ix < (unsigned)a.Wi;
-        const unsigned row = ok ? (unsigned)((bt * a.Hi + iy) * a.Wi + ix) : a.zero_row;
-        rowoff[i] = row * a.row_stride;
+        if constexpr (NORM) {                    // byte offset of the fp32 pixel; ~0: a pixel that is not image (written as zeros)
+            rowoff[i] = ok ? (unsigned)((bt * a.Hi + iy) * a.Wi + ix) * (unsigned)(a.Cin * 4) : ~0u;
+        } else {
+            const unsigned row = ok ? (unsigned)((bt * a.Hi + iy) * a.Wi + ix) : a.zero_row;
+            rowoff[i] = row * a.row_stride;
+        }
     }
     auto stage_patch = [&](int cc, unsigned char* buf) {
 #pragma unroll
@@ -759,6 +778,44 @@ __global__ __launch_bounds__(512, (NT < 4 ? 2 : 1)) void conv_patch_kernel(ConvA
 #pragma unroll
                 for (int pl = 0; pl < NS; ++pl) conv_dma16(a.ap + pl * a.a_plane_stride, off, buf + pl * ATILE + (32 * blk) * 32);
             }
+    };
+    // ---- on-load path: item i of chunk cc = the 8 channels cc * 16 + 8 * nsc of patch pixel 32 (wave + 8 i) + (lane >> 1)
+    const int nsc = dcp ^ ((lane >> 4) & 1);                      // = sc of stage_patch (bit 3 of the pixel index is bit 4 of the lane)
+    f32x4 nx0, nx1;
+    auto norm_load = [&](int cc, int i) {
+        const unsigned off = (rowoff[i] == ~0u ? 0u : rowoff[i]) + (unsigned)((cc * 16 + 8 * nsc) * 4);      // (not image: any valid pixel)
+        const unsigned char* p = reinterpret_cast<const unsigned char*>(a.xf) + off;
+        nx0 = *reinterpret_cast<const f32x4*>(p);                 // ordinary loads: neighbouring tiles re-read the halo through L2
+        nx1 = *reinterpret_cast<const f32x4*>(p + 16);
+    };
+    auto norm_store = [&](int cc, int i, unsigned char* buf) {
+        const um_const_f32p mu = (um_const_f32p)(unsigned long)(a.nstats + ((long)bt * 2) * a.Cin + cc * 16);
+        const um_const_f32p rs = mu + a.Cin;
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float m = nsc ? mu[8 + k] : mu[k], r = nsc ? rs[8 + k] : rs[k];
+            v[k] = ((k < 4 ? nx0[k & 3] : nx1[k & 3]) - m) * r;
+        }
+        if (a.norm_relu) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
+        }
+        const bool ok = rowoff[i] != ~0u;
+        u32x4 h = {T::pack2(v[0], v[1]), T::pack2(v[2], v[3]), T::pack2(v[4], v[5]), T::pack2(v[6], v[7])};
+        unsigned char* dst = buf + (32 * (wave + 8 * i)) * 32 + lane * 16;
+        if (NS == 2) {
+            u32x4 l;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const f32x2 u = T::unpack2(h[k]);
+                l[k] = ok ? T::pack2(v[2 * k] - u[0], v[2 * k + 1] - u[1]) : 0u;
+            }
+            *reinterpret_cast<u32x4*>(dst + ATILE) = l;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) h[k] = ok ? h[k] : 0u;
+        *reinterpret_cast<u32x4*>(dst) = h;
     };
     // the three weight tiles of kernel row ky: 3 NT blocks of 32 output rows, block q = (tap kx, rows 32 jb ..)
     auto stage_w = [&](int cc, int ky, unsigned char* buf) {
@@ -795,8 +852,18 @@ __global__ __launch_bounds__(512, (NT < 4 ? 2 : 1)) void conv_patch_kernel(ConvA
             foffa[ky][kx] = r * 32 + ((half ^ ((r >> 3) & 1)) << 4);
         }
 
-    stage_patch(0, lds);
-    stage_w(0, 0, lds + WBASE);
+    if constexpr (NORM) {
+        stage_w(0, 0, lds + WBASE);
+        norm_load(0, 0);
+        norm_store(0, 0, lds);
+        if (wave < 3) {
+            norm_load(0, 1);
+            norm_store(0, 1, lds);
+        }
+    } else {
+        stage_patch(0, lds);
+        stage_w(0, 0, lds + WBASE);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -811,7 +878,18 @@ __global__ __launch_bounds__(512, (NT < 4 ? 2 : 1)) void conv_patch_kernel(ConvA
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
                 if (kx == 0 && !last) stage_w(ky == 2 ? cc + 1 : cc, ky == 2 ? 0 : ky + 1, lds + w_nxt);
-                if (kx == 1 && ky == 0 && cc + 1 < cpt) stage_patch(cc + 1, lds + a_nxt);     // used from stage (cc + 1, 0) on
+                if constexpr (NORM) {                             // a_nxt is idle during the whole chunk; used from stage (cc + 1, 0) on
+                    if (kx == 1 && cc + 1 < cpt) {
+                        if (ky == 0) norm_load(cc + 1, 0);
+                        if (ky == 1) {
+                            norm_store(cc + 1, 0, lds + a_nxt);
+                            if (wave < 3) norm_load(cc + 1, 1);
+                        }
+                        if (ky == 2 && wave < 3) norm_store(cc + 1, 1, lds + a_nxt);
+                    }
+                } else {
+                    if (kx == 1 && ky == 0 && cc + 1 < cpt) stage_patch(cc + 1, lds + a_nxt);     // used from stage (cc + 1, 0) on
+                }
                 const i16x8 bh = *reinterpret_cast<const i16x8*>(lds + a_cur + foffa[ky][kx]);
                 i16x8 bl;
                 if (NS == 2) bl = *reinterpret_cast<const i16x8*>(lds + a_cur + ATILE + foffa[ky][kx]);
@@ -835,6 +913,18 @@ __global__ __launch_bounds__(512, (NT < 4 ? 2 : 1)) void conv_patch_kernel(ConvA
     const int nvalid = y0 + wave < a.Ho ? min(32, a.Wo - x0) : 0;               // this wave's pixels inside the image
     conv_epilogue<T, NS, NT, L::NTE>(a, acc, lds, lds + L::EPI, bt, (y0 + wave) * a.Wo + x0, nvalid, (bt * tpi + tt) * 2, true, n0, tid,
                                      wave, lane, half);
+}
+
+template <typename T, int NS, int NT>
+__global__ __launch_bounds__(512, (NT < 4 ? 2 : 1)) void conv_patch_kernel(ConvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    conv_patch_body<T, NS, NT, false>(a, lds);
+}
+
+template <typename T, int NS, int NT>
+__global__ __launch_bounds__(512, (NT < 4 ? 2 : 1)) void conv_patch_norm_kernel(ConvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    conv_patch_body<T, NS, NT, true>(a, lds);
 }
 
 // ------------------------------------------------------------------------------------ host side
@@ -885,7 +975,7 @@ static hipError_t launch_conv_rows(const ConvArgs& a, int mode, hipStream_t stre
     return hipGetLastError();
 }
 
-template <int NT>
+template <int NT, bool NORM = false>
 static hipError_t launch_conv_patch(const ConvArgs& a, int mode, hipStream_t stream) {
     static bool configured[2] = {false, false};    // opt in to > 64 KB of LDS once per instantiation
     dim3 grid(a.B * ((a.Ho + 7) / 8) * ((a.Wo + 31) / 32) * ((a.Cout + 32 * NT - 1) / (32 * NT))), block(512);
@@ -893,22 +983,29 @@ static hipError_t launch_conv_patch(const ConvArgs& a, int mode, hipStream_t str
     static_assert(LDS2 <= 160 * 1024 && LDS1 <= 160 * 1024, "ring beyond the CU's LDS");
     ScopedKernelTimer timer(UM_K_CONV, stream);
     um_census_hit(UM_V_CONV_PATCH);
+    if (NORM) um_census_hit(UM_V_CONV_PATCH_NORM);                // counted in addition: the operand path, not another tiling
+    void (*k2)(ConvArgs), (*k1)(ConvArgs);
+    if constexpr (NORM) {
+        k2 = conv_patch_norm_kernel<Fp16, 2, NT>;
+        k1 = conv_patch_norm_kernel<Bf16, 1, NT>;
+    } else {
+        k2 = conv_patch_kernel<Fp16, 2, NT>;
+        k1 = conv_patch_kernel<Bf16, 1, NT>;
+    }
     if (mode == 0) {
         if (!configured[0]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_patch_kernel<Fp16, 2, NT>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS2);
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, LDS2);
             if (e != hipSuccess) return e;
             configured[0] = true;
         }
-        hipLaunchKernelGGL((conv_patch_kernel<Fp16, 2, NT>), grid, block, LDS2, stream, a);
+        hipLaunchKernelGGL(k2, grid, block, LDS2, stream, a);
     } else {
         if (!configured[1]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_patch_kernel<Bf16, 1, NT>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS1);
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, LDS1);
             if (e != hipSuccess) return e;
             configured[1] = true;
         }
-        hipLaunchKernelGGL((conv_patch_kernel<Bf16, 1, NT>), grid, block, LDS1, stream, a);
+        hipLaunchKernelGGL(k1, grid, block, LDS1, stream, a);
     }
     return hipGetLastError();
 }
@@ -938,6 +1035,22 @@ static ConvKind conv_pick(int hi, int wi, int ho, int wo, int cout, int kh, int 
     return rows3 || rows5 ? CONV_ROWS : CONV_GENERIC;
 }
 
+// ---- the normalise-on-load operand path: which tile widths of the patch kernel take it.  Decided per width by measurement on
+// MI355X (profiles/norm_on_load_ab.txt: conv2(on load) against apply + conv2(planes) at the encoder's layer shapes); a width that
+// lost stays on the normalisation pass.  A compile-time table: no environment variable, no device state.
+static constexpr bool kNormOnLoad[5] = {false, false, true, true, true};       // index = NT
+
+extern "C" int um_conv2d_norm_supported(int hi, int wi, int cin, int cout, int kh, int kw, int stride, int pad_h, int pad_w, int mode) {
+    if (hi <= 0 || wi <= 0 || cin <= 0 || cin % 32 != 0 || cout <= 0 || cout % 4 != 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad_h < 0 ||
+        pad_w < 0 || (mode != 0 && mode != 1))
+        return 0;
+    const int ho = (hi + 2 * pad_h - kh) / stride + 1, wo = (wi + 2 * pad_w - kw) / stride + 1;
+    if (ho <= 0 || wo <= 0) return 0;
+    int nt;
+    if (conv_pick(hi, wi, ho, wo, cout, kh, kw, stride, pad_h, pad_w, &nt) != CONV_PATCH) return 0;
+    return nt >= 2 && nt <= 4 && kNormOnLoad[nt] ? 1 : 0;
+}
+
 extern "C" int um_conv_stats_parts(int hi, int wi, int cout, int kh, int kw, int stride, int pad_h, int pad_w) {
     if (hi <= 0 || wi <= 0 || cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad_h < 0 || pad_w < 0) return -1;
     const int ho = (hi + 2 * pad_h - kh) / stride + 1, wo = (wi + 2 * pad_w - kw) / stride + 1;
@@ -952,7 +1065,8 @@ static int conv2d_impl(const void* a_planes, int a_ld, int a_coff, long a_rows, 
                        float* stats_out, int batch, int hi, int wi, int cin, int cout, int kh, int kw, int stride,
                        int pad_h, int pad_w, int act, int wshift, int mode, void* stream_, int gate, float* gate_h,
                        const float* gate_z, int gate_zld, const float* addend = nullptr, int addend_ld = 0, float* gate_hout = nullptr,
-                       int gate_hout_ld = 0) {
+                       int gate_hout_ld = 0, const float* norm_x = nullptr, const float* norm_stats = nullptr, int norm_relu = 0) {
+    const bool norm = norm_x != nullptr;                          // um_conv2d_norm_fwd: fp32 input + statistics instead of a_planes
     if (gate_hout && (gate != 2 || gate_hout_ld < cout || gate_hout_ld % 4 != 0 || ((unsigned long)gate_hout & 15) != 0)) {
         um_set_error("um_conv2d: a separate new-state tensor goes with gate 2 only: 16-byte aligned fp32 [M][ld >= channels, ld %% 4 == 0]");
         return -1;
@@ -961,7 +1075,7 @@ static int conv2d_impl(const void* a_planes, int a_ld, int a_coff, long a_rows, 
         um_set_error("um_conv2d: the addend must be 16-byte aligned fp32 [M][ld >= cout, ld %% 4 == 0] (and excludes fused statistics)");
         return -1;
     }
-    if (!a_planes || !w_planes || (!out && !out_planes) || batch <= 0 || hi <= 0 || wi <= 0 || cin <= 0 || cin % 32 != 0 ||
+    if ((!a_planes && !norm) || !w_planes || (!out && !out_planes) || batch <= 0 || hi <= 0 || wi <= 0 || cin <= 0 || cin % 32 != 0 ||
         cout <= 0 || cout % 4 != 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad_h < 0 || pad_w < 0 || (mode != 0 && mode != 1) ||
         wshift < 0 || wshift > 14 || act < 0 || act > 3) {
         um_set_error("um_conv2d: bad argument (batch=%d hi=%d wi=%d cin=%d cout=%d k=%dx%d stride=%d pad=%d,%d act=%d; cin must "
@@ -993,7 +1107,25 @@ static int conv2d_impl(const void* a_planes, int a_ld, int a_coff, long a_rows, 
         um_set_error("um_conv2d: operand planes beyond 4 GiB are not addressable by this kernel");
         return -4;
     }
+    if (norm) {
+        if (!norm_stats || ((unsigned long)norm_x & 15) != 0 || ((unsigned long)norm_stats & 3) != 0) {
+            um_set_error("um_conv2d_norm_fwd: the fp32 input must be 16-byte aligned and comes with its statistics [batch][2][cin]");
+            return -1;
+        }
+        if (!um_conv2d_norm_supported(hi, wi, cin, cout, kh, kw, stride, pad_h, pad_w, mode)) {
+            um_set_error("um_conv2d_norm_fwd: no on-load kernel for this geometry (hi=%d wi=%d cin=%d cout=%d k=%dx%d stride=%d pad=%d,%d): "
+                         "ask um_conv2d_norm_supported() first", hi, wi, cin, cout, kh, kw, stride, pad_h, pad_w);
+            return -2;
+        }
+        if (rows_in * cin * 4 >= (1L << 32) - 1) {
+            um_set_error("um_conv2d_norm_fwd: an fp32 input beyond 4 GiB is not addressable by this kernel");
+            return -4;
+        }
+    }
     ConvArgs a;
+    a.xf = norm_x;
+    a.nstats = norm_stats;
+    a.norm_relu = norm_relu;
     a.ap = (const unsigned short*)a_planes + a_coff;
     a.a_plane_stride = a_rows * a_ld;
     a.row_stride = (unsigned)a_ld * 2;
@@ -1038,7 +1170,9 @@ static int conv2d_impl(const void* a_planes, int a_ld, int a_coff, long a_rows, 
     int nt;
     const ConvKind kind = conv_pick(hi, wi, ho, wo, cout, kh, kw, stride, pad_h, pad_w, &nt);
     hipStream_t st = (hipStream_t)stream_;
-    if (kind == CONV_PATCH)
+    if (norm)                                                     // (um_conv2d_norm_supported above: patch kernel, NT = 2 .. 4)
+        e = nt == 2 ? launch_conv_patch<2, true>(a, mode, st) : nt == 3 ? launch_conv_patch<3, true>(a, mode, st) : launch_conv_patch<4, true>(a, mode, st);
+    else if (kind == CONV_PATCH)
         e = nt == 1 ? launch_conv_patch<1>(a, mode, st) : nt == 2 ? launch_conv_patch<2>(a, mode, st) : nt == 3 ? launch_conv_patch<3>(a, mode, st)
                                                                                                           : launch_conv_patch<4>(a, mode, st);
     else if (kind == CONV_ROWS && kw == 5) e = launch_conv_rows<4, 5, 2>(a, mode, st);
@@ -1108,6 +1242,22 @@ extern "C" int um_conv2d_fwd(const void* a_planes, const void* w_planes, const f
     const long rows_in = (long)batch * hi * wi;
     return um_conv2d_ex(a_planes, cin, 0, rows_in + 1, w_planes, bias, out, cout, 0, nullptr, 0, 0, 0, stats_out, batch, hi, wi,
                         cin, cout, kh, kw, stride, pad_h, pad_w, relu ? 1 : 0, wshift, mode, stream_);
+}
+
+// um_conv2d_fwd whose input is the producing convolution's fp32 NHWC output x [batch*hi*wi][cin] and its finalized InstanceNorm
+// statistics [batch][2][cin] (um_nhwc_stats_finalize): relu?((x - mean) * rstd) is computed while the operand is staged
+// (conv_patch_norm_kernel), bit-identical to um_nhwc_instance_norm(planes) -> um_conv2d_fwd without that pass over memory.
+extern "C" int um_conv2d_norm_fwd(const float* x, const float* norm_stats, int norm_relu, const void* w_planes, const float* bias, float* out,
+                                  float* stats_out, int batch, int hi, int wi, int cin, int cout, int kh, int kw, int stride, int pad_h,
+                                  int pad_w, int relu, int wshift, int mode, void* stream_) {
+    if (!x) {
+        um_set_error("um_conv2d_norm_fwd: no input");
+        return -1;
+    }
+    const long rows_in = (long)batch * hi * wi;
+    return conv2d_impl(nullptr, cin, 0, rows_in + 1, w_planes, bias, out, cout, 0, nullptr, 0, 0, 0, stats_out, batch, hi, wi, cin, cout, kh,
+                       kw, stride, pad_h, pad_w, relu ? 1 : 0, wshift, mode, stream_, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, x,
+                       norm_stats, norm_relu ? 1 : 0);
 }
 
 // ---- 7x7 convolutions with very few input channels on the same kernel ----------------------------------------------------
@@ -1243,6 +1393,8 @@ extern "C" int um_conv7_fwd(const float* image, int channels, int normalize, con
     a.gate_z = nullptr;
     a.out_scale = ldexpf(1.f, -wshift);
     a.xcd = conv_xcd_enabled();
+    a.xf = a.nstats = nullptr;
+    a.norm_relu = 0;
     hipError_t e;
     if (cout % 128 == 0 || cout > 192) e = launch_conv<4>(a, 0, stream);
     else if (cout % 96 == 0) e = launch_conv<3>(a, 0, stream);

@@ -387,6 +387,25 @@ extern "C" int um_nhwc_instance_norm(const float* x, const float* shortcut, cons
     return 0;
 }
 
+extern "C" int um_nhwc_stats_finalize(const float* conv_stats, int conv_stats_parts, float* stats_out, int batch, int pixels, int channels,
+                                      float eps, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!conv_stats || conv_stats_parts <= 0 || !stats_out || batch <= 0 || pixels <= 0 || !nhwc_channels_ok(channels)) {
+        um_set_error("um_nhwc_stats_finalize: bad argument (parts=%d batch=%d pixels=%d channels=%d: channels must be a multiple of 8, "
+                     "<= 256)", conv_stats_parts, batch, pixels, channels);
+        return -1;
+    }
+    ScopedKernelTimer timer(UM_K_INSTANCE_NORM, stream);
+    hipLaunchKernelGGL(nhwc_stats_finalize_kernel, dim3(channels / 8, batch), dim3(256), 0, stream, conv_stats, stats_out, pixels, channels,
+                       conv_stats_parts, 0, eps);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        um_set_error("um_nhwc_stats_finalize: launch failed: %s", hipGetErrorString(e));
+        return (int)e;
+    }
+    return 0;
+}
+
 extern "C" int um_nchw_to_nhwc(const float* x, void* planes_out, float* f32_out, int batch, int channels, int pixels, int mode,
                                void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;

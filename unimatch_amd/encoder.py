@@ -47,8 +47,12 @@ class _Residual(nn.Module):
         stride = self.conv1.stride[0]
         cout = self.conv1.out_channels
         t, ho, wo = ops.conv2d_nhwc((planes, b, h, w, c), self.conv1.weight, None, stride, (1, 1), stats=True)
-        tp, _ = ops.nhwc_norm(t, b, ho * wo, relu=True, want_planes=True, conv_stats=ops.last_conv_stats)
-        u, _, _ = ops.conv2d_nhwc((tp, b, ho, wo, cout), self.conv2.weight, None, 1, (1, 1), stats=True)
+        if getattr(ops, 'norm_on_load', False) and ops.conv2d_norm_supported(ho, wo, cout, self.conv2.weight):
+            # the middle normalisation has one reader: conv2 normalises t while it stages its operand, no planes of t exist
+            u, _, _ = ops.conv2d_nhwc_normed(t, ops.last_conv_stats, (b, ho, wo, cout), self.conv2.weight, stats=True)
+        else:
+            tp, _ = ops.nhwc_norm(t, b, ho * wo, relu=True, want_planes=True, conv_stats=ops.last_conv_stats)
+            u, _, _ = ops.conv2d_nhwc((tp, b, ho, wo, cout), self.conv2.weight, None, 1, (1, 1), stats=True)
         ustats = ops.last_conv_stats
         sc = scp = None
         if self.downsample is None:

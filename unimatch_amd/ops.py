@@ -153,6 +153,7 @@ class HipOps(WorkspaceRegistry):
     fused_kv = True            # ... which, from block 1 on, is the previous block's FFN epilogue (um_ffn_kv_fwd): no launch at all
     # (class attributes: tests and tools/ab_bench.py flip them programmatically; the product reads no environment variable)
     fused_conv = True          # encoder convolutions + InstanceNorm in NHWC on um_conv2d_fwd / um_nhwc_instance_norm
+    norm_on_load = True        # ... a residual block's middle InstanceNorm + ReLU inside its second convolution (um_conv2d_norm_fwd)
     CONV_MODE = 0              # ... always in the exact arithmetic: 'fast' (bf16) is a property of the matching path only
     WSHIFT = 10                # weights are scaled by 2^10 before the fp16 split (exact), see linear.hip
 
@@ -601,6 +602,42 @@ class HipOps(WorkspaceRegistry):
             stride, ph, pw, int(bool(relu)), self.WSHIFT, self.CONV_MODE, _stream()), meta)
         _abi.check(code, 'um_conv2d_fwd')
         return out, ho, wo
+
+    def conv2d_norm_supported(self, h, w, cin, weight, stride=1, padding=(1, 1)):
+        """True when ``conv2d_nhwc_normed`` serves this convolution (``um_conv2d_norm_supported``: a pure function of the geometry)."""
+        cout, wcin, kh, kw = weight.shape
+        ph, pw = (padding, padding) if isinstance(padding, int) else padding
+        return wcin == cin and bool(self.lib.um_conv2d_norm_supported(h, w, cin, cout, kh, kw, stride, ph, pw, self.CONV_MODE))
+
+    def conv2d_nhwc_normed(self, x, conv_stats, geom, weight, bias=None, norm_relu=True, relu=False, stats=False, eps=1e-5):
+        """``conv2d_nhwc`` (3x3, stride 1, pad 1) of ``relu(instance_norm(x))`` where ``x`` is the fp32 NHWC output ``[b*h*w, cin]`` of
+        the producing convolution and ``conv_stats`` the ``last_conv_stats`` it left: the statistics are finalized
+        (``um_nhwc_stats_finalize``) and the convolution normalises while it stages its operand (``um_conv2d_norm_fwd``) -- the
+        results of ``nhwc_norm`` + ``conv2d_nhwc`` bit for bit, without the normalisation's pass over memory."""
+        b, h, w, cin = geom
+        self._check_rows('x', x, cin)
+        if x.shape[0] != b * h * w:
+            raise ValueError('conv2d_nhwc_normed: x must have b * h * w rows')
+        wp, cout, wcin, kh, kw = self.conv_weight_planes(weight)
+        if wcin != cin:
+            raise ValueError(f'conv2d_nhwc_normed: weight expects {wcin} input channels, activation has {cin}')
+        nstats = torch.empty((b, 2, cin), dtype=torch.float32, device=x.device)          # per call: one buffer per stream lane
+        _abi.check(self._launch('instance_norm', lambda: self.lib.um_nhwc_stats_finalize(
+            _ptr(conv_stats[0]), conv_stats[1], _ptr(nstats), b, h * w, cin, float(eps), _stream())), 'um_nhwc_stats_finalize')
+        out = torch.empty((b * h * w, cout), dtype=torch.float32, device=x.device)
+        self.last_conv_stats = None
+        if stats:
+            parts = self.lib.um_conv_stats_parts(h, w, cout, kh, kw, 1, 1, 1)
+            self.last_conv_stats = (torch.empty(self.lib.um_conv_stats_bytes(b, parts, cout) // 4, dtype=torch.float32,
+                                                device=x.device), parts)
+        st = self.last_conv_stats[0] if self.last_conv_stats is not None else None
+        meta = {'flops': 2.0 * b * h * w * cout * kh * kw * cin}
+        code = self._launch('conv', lambda: self.lib.um_conv2d_norm_fwd(
+            _ptr(x), _ptr(nstats), int(bool(norm_relu)), _ptr(wp), _ptr(bias) if bias is not None else None, _ptr(out),
+            _ptr(st) if st is not None else None, b, h, w, cin, cout, kh, kw, 1, 1, 1, int(bool(relu)), self.WSHIFT, self.CONV_MODE,
+            _stream()), meta)
+        _abi.check(code, 'um_conv2d_norm_fwd')
+        return out, h, w
 
     def nhwc_planes_from(self, pieces, pad_to=32):
         """Operand planes of the channel concatenation of fp32 NHWC pieces ``[rows, c_i]`` (zero-padded to a multiple of
