@@ -519,6 +519,39 @@ int um_fwd_bwd_occlusion(const float* fwd, const float* bwd, float* occ_fwd, flo
 size_t um_flow_to_rgb_workspace_bytes(int batch, int h, int w);
 int um_flow_to_rgb(const float* flow, unsigned char* rgb, int batch, int h, int w, void* workspace, size_t ws_bytes, void* stream);
 
+/* Evaluation metrics (csrc/metrics.hip): the statistics of the reference's validation loops, reduced on the device.  `pred` is the
+ * batch as the model returned it, STILL PADDED ([B,2,hp,wp] flow, [B,hp,wp] disparity / depth); ground truth and masks are
+ * [B,(2,)h,w] fp32, and ground-truth pixel (y, x) is compared with pred pixel (y + top, x + left): the InputPadder's crop, read in
+ * place.  0 <= top, top + h <= hp, 0 <= left, left + w <= wp, else UM_ERR_BAD_ARG.  Each call writes one row of float64 accumulators
+ * per sample into rows[B][K] (counts are float64 too: exact below 2^53).  Per-pixel quantities are the reference's float32 values
+ * bit for bit (separately rounded products and sums, correctly rounded sqrt and division); only the accumulation is float64.
+ * Two launches (one partial row per 2048 pixels into `workspace`, then a fixed-order fold per sample): no atomics, no counters,
+ * every workspace slot of the launch's geometry is rewritten by each call, so rows are bitwise reproducible and do not depend on how
+ * samples were batched.  workspace (8-byte aligned) >= the matching *_workspace_bytes query (0 for bad sizes).
+ *   um_flow_metrics   over valid >= 0.5 (NULL: every pixel), epe = |pred - gt|, mag = |gt|:
+ *                     0 n | 1 sum epe | 2..4 n of epe > 1, 3, 5 | 5 n of epe > 3 and epe / mag > 0.05 (KITTI outliers) |
+ *                     6,7 n and sum epe of mag < 10 | 8,9 of 10 <= mag <= 40 | 10,11 of mag > 40 | with noc_valid (else zeros):
+ *                     12,13 n and sum epe of matched pixels (noc_valid > 0.5 and the ground-truth target in frame:
+ *                     0 <= x + u <= w - 1, 0 <= y + v <= h - 1, |u| <= w - 1, |v| <= h - 1) | 14,15 of the unmatched ones.
+ *   um_disp_metrics   over gt > 0 (and gt < max_disp when max_disp > 0), e = |gt - pred|:
+ *                     0 n | 1 sum e | 2..4 n of e > 1, 2, 3 | 5 n of e > 3 and e / gt > 0.05 (D1) |
+ *                     6 n of e > 10 and e / max(gt, 1) > 0.1 (bad pixel) | 7 zero.
+ *   um_depth_metrics  over lo < gt < hi and valid > 0.5 (NULL: no mask):
+ *                     0 n | 1 sum |gt - pred| / gt | 2 sum (gt - pred)^2 / gt | 3 sum (gt - pred)^2 | 4 sum (ln gt - ln pred)^2,
+ *                     float64 logarithms of the float32 values | 5..7 n of max(gt / pred, pred / gt) < 1.25, 1.25^2, 1.25^3. */
+#define UM_FLOW_METRICS_K 16
+#define UM_DISP_METRICS_K 8
+#define UM_DEPTH_METRICS_K 8
+size_t um_flow_metrics_workspace_bytes(int batch, int h, int w);
+int um_flow_metrics(const float* pred, const float* gt, const float* valid, const float* noc_valid, double* rows, int batch, int hp,
+                    int wp, int h, int w, int top, int left, void* workspace, size_t ws_bytes, void* stream);
+size_t um_disp_metrics_workspace_bytes(int batch, int h, int w);
+int um_disp_metrics(const float* pred, const float* gt, double* rows, int batch, int hp, int wp, int h, int w, int top, int left,
+                    float max_disp, void* workspace, size_t ws_bytes, void* stream);
+size_t um_depth_metrics_workspace_bytes(int batch, int h, int w);
+int um_depth_metrics(const float* pred, const float* gt, const float* valid, double* rows, int batch, int hp, int wp, int h, int w,
+                     int top, int left, float lo, float hi, void* workspace, size_t ws_bytes, void* stream);
+
 /* The per-scale loop's small glue ops (round 3: they were torch calls):
  *   um_flow_upsample2x  out[B,V,2h,2w] = mult * bilinear_up2(flow[B,V,h,w]), align_corners = True -- unimatch/unimatch.py:162-163
  *                       (F.interpolate(..., scale_factor=2, mode='bilinear', align_corners=True) * 2: pass mult = 2)

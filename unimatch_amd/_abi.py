@@ -73,6 +73,12 @@ SIGNATURES = {
     'um_fwd_bwd_occlusion': (_c_int, [_c_void_p] * 4 + [_c_int] * 3 + [ctypes.c_float] * 2 + [_c_void_p]),
     'um_flow_to_rgb_workspace_bytes': (_c_size_t, [_c_int] * 3),
     'um_flow_to_rgb': (_c_int, [_c_void_p] * 2 + [_c_int] * 3 + [_c_void_p, _c_size_t, _c_void_p]),
+    'um_flow_metrics_workspace_bytes': (_c_size_t, [_c_int] * 3),
+    'um_flow_metrics': (_c_int, [_c_void_p] * 5 + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p]),
+    'um_disp_metrics_workspace_bytes': (_c_size_t, [_c_int] * 3),
+    'um_disp_metrics': (_c_int, [_c_void_p] * 3 + [_c_int] * 7 + [ctypes.c_float, _c_void_p, _c_size_t, _c_void_p]),
+    'um_depth_metrics_workspace_bytes': (_c_size_t, [_c_int] * 3),
+    'um_depth_metrics': (_c_int, [_c_void_p] * 4 + [_c_int] * 7 + [ctypes.c_float] * 2 + [_c_void_p, _c_size_t, _c_void_p]),
     'um_convex_upsample': (_c_int, [_c_void_p] * 3 + [_c_int] * 7 + [_c_void_p]),
     'um_flow_upsample2x': (_c_int, [_c_void_p] * 2 + [_c_int] * 4 + [ctypes.c_float, _c_void_p]),
     'um_depth_cam_pack': (_c_int, [_c_void_p] * 3 + [_c_int, ctypes.c_float, _c_int, _c_void_p]),

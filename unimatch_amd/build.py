@@ -12,15 +12,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libunimatch_hip.so')
 SOURCES = ['capi.hip', 'global_match.hip', 'window_attn.hip', 'local_ops.hip', 'linear.hip', 'ffn.hip', 'conv.hip', 'nhwc_ops.hip', 'norm_ops.hip', 'upsample.hip',
-           'rccl_gather.hip', 'local_corr_mfma.hip', 'aliases.hip', 'probe.hip', 'video.hip']
+           'rccl_gather.hip', 'local_corr_mfma.hip', 'aliases.hip', 'probe.hip', 'video.hip', 'metrics.hip']
 # hardware micro-benchmarks (um_debug_*): diagnostic builds only, never in the shipped library
 DIAG_SOURCES = ['microbench.hip']
 HEADERS = ['common.h', 'planes.h', 'timing.h', os.path.join('..', '..', 'include', 'unimatch_hip.h')]
 # per-file extras: the FFN kernel's hand-placed scalar VALU stream must not be re-packed into v_pk_* by the SLP vectorizer
 EXTRA_FLAGS = {'ffn.hip': ['-fno-slp-vectorize'], 'global_match.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form', '-Wno-inline-asm'], 'window_attn.hip': ['-fno-slp-vectorize'],
                'linear.hip': ['-fno-slp-vectorize'],
-               # the post-processing kernels round every product and sum separately, as the reference's NumPy / ATen steps do
-               'video.hip': ['-ffp-contract=off']}
+               # the post-processing and metric kernels round every product and sum separately, as the reference's NumPy / ATen steps do
+               'video.hip': ['-ffp-contract=off'],
+               # ... and take IEEE square roots and quotients (hipcc's default, stated because the results depend on it)
+               'metrics.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt']}
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result']
 
 

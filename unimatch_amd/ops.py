@@ -515,6 +515,67 @@ class HipOps(WorkspaceRegistry):
         _abi.check(code, 'um_flow_to_rgb')
         return rgb
 
+    # ------------------------------------------------------------------ evaluation metrics
+    @staticmethod
+    def _metric_args(name, pred, gt, channels, crop, masks):
+        """Shape / dtype checks shared by the three metric wrappers: ``pred`` still padded, ``gt`` and the masks at the crop's size.
+        Returns the contiguous tensors and ``(b, hp, wp, h, w, top, left)``."""
+        want = 4 if channels else 3
+        ok = (pred.is_cuda and pred.dtype == torch.float32 and gt.dtype == torch.float32 and gt.device == pred.device
+              and pred.dim() == want and gt.dim() == want and gt.shape[0] == pred.shape[0]
+              and (not channels or (pred.shape[1] == channels and gt.shape[1] == channels)))
+        if not ok:
+            raise ValueError(f'{name}: expected CUDA float32 pred / gt of {want} dimensions and one batch, got {tuple(pred.shape)} '
+                             f'{pred.dtype} and {tuple(gt.shape)} {gt.dtype}')
+        b, (hp, wp), (h, w) = pred.shape[0], pred.shape[-2:], gt.shape[-2:]
+        top, left = (int(crop[0]), int(crop[1])) if crop is not None else (0, 0)
+        if top < 0 or left < 0 or top + h > hp or left + w > wp:
+            raise ValueError(f'{name}: the crop {h}x{w} at ({top}, {left}) leaves the prediction {hp}x{wp}')
+        out = []
+        for m in masks:
+            if m is not None:
+                if not (m.is_cuda and m.device == pred.device and tuple(m.shape) == (b, h, w)):
+                    raise ValueError(f'{name}: expected a CUDA mask [{b}, {h}, {w}], got {tuple(m.shape)} on {m.device}')
+                m = m.float().contiguous()
+            out.append(m)
+        return pred.contiguous(), gt.contiguous(), out, (b, hp, wp, h, w, top, left)
+
+    def flow_metrics(self, pred, gt, valid=None, noc_valid=None, crop=None):
+        """``um_flow_metrics``: one row ``[16]`` float64 of end-point-error accumulators per sample (layout in the header) of the
+        padded prediction ``pred [B, 2, Hp, Wp]`` against ``gt [B, 2, H, W]`` at the crop offset ``crop = (top, left)``; ``valid``,
+        ``noc_valid`` ``[B, H, W]`` or None.  Enqueued on the current stream: no synchronisation, no copy."""
+        pred, gt, (valid, noc_valid), (b, hp, wp, h, w, top, left) = self._metric_args('flow_metrics', pred, gt, 2, crop, (valid, noc_valid))
+        rows = torch.empty((b, 16), dtype=torch.float64, device=pred.device)
+        ws = self._ws(self.lib.um_flow_metrics_workspace_bytes(b, h, w), pred.device)
+        code = self._launch('flow_metrics', lambda: self.lib.um_flow_metrics(
+            _ptr(pred), _ptr(gt), _ptr(valid) if valid is not None else None, _ptr(noc_valid) if noc_valid is not None else None,
+            _ptr(rows), b, hp, wp, h, w, top, left, _ptr(ws), ws.numel(), _stream()))
+        _abi.check(code, 'um_flow_metrics')
+        return rows
+
+    def disp_metrics(self, pred, gt, max_disp=0.0, crop=None):
+        """``um_disp_metrics``: one row ``[8]`` float64 per sample of ``pred [B, Hp, Wp]`` against ``gt [B, H, W]`` over ``gt > 0``
+        (and ``gt < max_disp`` when ``max_disp > 0``)."""
+        pred, gt, _, (b, hp, wp, h, w, top, left) = self._metric_args('disp_metrics', pred, gt, 0, crop, ())
+        rows = torch.empty((b, 8), dtype=torch.float64, device=pred.device)
+        ws = self._ws(self.lib.um_disp_metrics_workspace_bytes(b, h, w), pred.device)
+        code = self._launch('disp_metrics', lambda: self.lib.um_disp_metrics(
+            _ptr(pred), _ptr(gt), _ptr(rows), b, hp, wp, h, w, top, left, float(max_disp), _ptr(ws), ws.numel(), _stream()))
+        _abi.check(code, 'um_disp_metrics')
+        return rows
+
+    def depth_metrics(self, pred, gt, valid=None, lo=0.0, hi=float('inf'), crop=None):
+        """``um_depth_metrics``: one row ``[8]`` float64 per sample of ``pred [B, Hp, Wp]`` against ``gt [B, H, W]`` over
+        ``lo < gt < hi`` and ``valid > 0.5``."""
+        pred, gt, (valid,), (b, hp, wp, h, w, top, left) = self._metric_args('depth_metrics', pred, gt, 0, crop, (valid,))
+        rows = torch.empty((b, 8), dtype=torch.float64, device=pred.device)
+        ws = self._ws(self.lib.um_depth_metrics_workspace_bytes(b, h, w), pred.device)
+        code = self._launch('depth_metrics', lambda: self.lib.um_depth_metrics(
+            _ptr(pred), _ptr(gt), _ptr(valid) if valid is not None else None, _ptr(rows), b, hp, wp, h, w, top, left, float(lo),
+            float(hi), _ptr(ws), ws.numel(), _stream()))
+        _abi.check(code, 'um_depth_metrics')
+        return rows
+
     def flow_upsample2x(self, flow, mult=2.0):
         """``mult * F.interpolate(flow, scale_factor=2, mode='bilinear', align_corners=True)`` (``um_flow_upsample2x``)."""
         if not (flow.is_cuda and flow.dtype == torch.float32 and flow.dim() == 4):
