@@ -552,6 +552,42 @@ size_t um_depth_metrics_workspace_bytes(int batch, int h, int w);
 int um_depth_metrics(const float* pred, const float* gt, const float* valid, double* rows, int batch, int hp, int wp, int h, int w,
                      int top, int left, float lo, float hi, void* workspace, size_t ws_bytes, void* stream);
 
+/* Inference-size handling (csrc/prepost.hip): the block the reference's evaluation scripts repeat around the forward
+ * (evaluate_flow.py:713-758, evaluate_stereo.py:340-375, evaluate_depth.py:78-129), as two memory-bound launches without state,
+ * workspace or atomics.  "Image space" is the frame after the optional transpose: ih x iw = (transpose ? w x h : h x w).
+ *   um_image_prepare  src: `batch` images of stored size h x w, UM_IMG_F32_NCHW [B,3,h,w] fp32 or UM_IMG_U8_NHWC [B,h,w,3] uint8 (a
+ *                     decoder's frames) -> dst [B,3,hp,wp] fp32, in this order:
+ *                       1. transpose != 0: H and W swap (the reference transposes tall inputs, evaluate_flow.py:713-717);
+ *                       2. mean, std != NULL (HOST arrays of 3, as in um_conv7_fwd; both or neither, std != 0):
+ *                          (x / 255 - mean) / std, three separately rounded fp32 operations (dataloader/stereo/transforms.py:20-63);
+ *                          flow passes raw 0..255 values and NULL;
+ *                       3. UM_SIZE_PAD: replicate padding with the image at (top, left): top + ih <= hp, left + iw <= wp (the
+ *                          InputPadder geometry in both its modes), or UM_SIZE_RESIZE: bilinear, align_corners=True (top, left unused).
+ *   um_pred_restore   the inverse, for a prediction pred [B,C,hp,wp] fp32 -> out [B,C,h,w] fp32 (C = 2 for UM_PRED_FLOW, 1 for
+ *                     UM_PRED_DISPARITY / UM_PRED_DEPTH): UM_SIZE_PAD crops ih x iw at (top, left); UM_SIZE_RESIZE resizes to
+ *                     ih x iw and rescales, a multiply and then a divide as the reference writes it: flow u * iw / wp and
+ *                     v * ih / hp (evaluate_flow.py:754-755), disparity * iw / wp (evaluate_stereo.py:375), depth nothing
+ *                     (evaluate_depth.py:131).  transpose != 0: the result is transposed back into h x w.  The flow CHANNELS ARE NOT
+ *                     SWAPPED by that transpose: channel 0 is still the displacement along image-space x, exactly as the reference
+ *                     leaves it (evaluate_flow.py:757-758).
+ * Bilinear arithmetic is ATen's, in fp32: scale = float(in - 1) / float(out - 1) (0 when out == 1), src = scale * dst, i0 = (int)src,
+ * i1 = min(i0 + 1, in - 1), l1 = src - i0, l0 = 1 - l1; the horizontal blends l0 a + l1 b of image space first, then the vertical one;
+ * no fused multiply-add.  The reference's numbers come from F.interpolate, so this mirrors it rather than an exact rational
+ * coordinate.  batch * C <= 65535 and every one of h, w, hp, wp <= UM_PREPOST_MAX_DIM (rows are spread over one grid dimension);
+ * a bad argument returns UM_ERR_BAD_ARG. */
+#define UM_PREPOST_MAX_DIM 262140
+#define UM_IMG_F32_NCHW 0
+#define UM_IMG_U8_NHWC 1
+#define UM_SIZE_PAD 0
+#define UM_SIZE_RESIZE 1
+#define UM_PRED_FLOW 0
+#define UM_PRED_DISPARITY 1
+#define UM_PRED_DEPTH 2
+int um_image_prepare(const void* src, int src_layout, float* dst, int batch, int h, int w, int transpose, const float* mean,
+                     const float* std, int mode, int hp, int wp, int top, int left, void* stream);
+int um_pred_restore(const float* pred, float* out, int batch, int channels, int hp, int wp, int mode, int top, int left, int h, int w,
+                    int kind, int transpose, void* stream);
+
 /* The per-scale loop's small glue ops (round 3: they were torch calls):
  *   um_flow_upsample2x  out[B,V,2h,2w] = mult * bilinear_up2(flow[B,V,h,w]), align_corners = True -- unimatch/unimatch.py:162-163
  *                       (F.interpolate(..., scale_factor=2, mode='bilinear', align_corners=True) * 2: pass mult = 2)

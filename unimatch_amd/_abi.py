@@ -79,6 +79,9 @@ SIGNATURES = {
     'um_disp_metrics': (_c_int, [_c_void_p] * 3 + [_c_int] * 7 + [ctypes.c_float, _c_void_p, _c_size_t, _c_void_p]),
     'um_depth_metrics_workspace_bytes': (_c_size_t, [_c_int] * 3),
     'um_depth_metrics': (_c_int, [_c_void_p] * 4 + [_c_int] * 7 + [ctypes.c_float] * 2 + [_c_void_p, _c_size_t, _c_void_p]),
+    'um_image_prepare': (_c_int, [_c_void_p, _c_int, _c_void_p] + [_c_int] * 4 + [ctypes.POINTER(ctypes.c_float)] * 2 + [_c_int] * 5 +
+                         [_c_void_p]),
+    'um_pred_restore': (_c_int, [_c_void_p] * 2 + [_c_int] * 11 + [_c_void_p]),
     'um_convex_upsample': (_c_int, [_c_void_p] * 3 + [_c_int] * 7 + [_c_void_p]),
     'um_flow_upsample2x': (_c_int, [_c_void_p] * 2 + [_c_int] * 4 + [ctypes.c_float, _c_void_p]),
     'um_depth_cam_pack': (_c_int, [_c_void_p] * 3 + [_c_int, ctypes.c_float, _c_int, _c_void_p]),

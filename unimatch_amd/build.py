@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libunimatch_hip.so')
 SOURCES = ['capi.hip', 'global_match.hip', 'window_attn.hip', 'local_ops.hip', 'linear.hip', 'ffn.hip', 'conv.hip', 'nhwc_ops.hip', 'norm_ops.hip', 'upsample.hip',
-           'rccl_gather.hip', 'local_corr_mfma.hip', 'aliases.hip', 'probe.hip', 'video.hip', 'metrics.hip']
+           'rccl_gather.hip', 'local_corr_mfma.hip', 'aliases.hip', 'probe.hip', 'video.hip', 'metrics.hip', 'prepost.hip']
 # hardware micro-benchmarks (um_debug_*): diagnostic builds only, never in the shipped library
 DIAG_SOURCES = ['microbench.hip']
 HEADERS = ['common.h', 'planes.h', 'timing.h', os.path.join('..', '..', 'include', 'unimatch_hip.h')]
@@ -22,7 +22,9 @@ EXTRA_FLAGS = {'ffn.hip': ['-fno-slp-vectorize'], 'global_match.hip': ['-fno-slp
                # the post-processing and metric kernels round every product and sum separately, as the reference's NumPy / ATen steps do
                'video.hip': ['-ffp-contract=off'],
                # ... and take IEEE square roots and quotients (hipcc's default, stated because the results depend on it)
-               'metrics.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt']}
+               'metrics.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
+               # the resize / normalise kernels are compared bit for bit with a host restatement of the same operation order
+               'prepost.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt']}
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result']
 
 

@@ -472,6 +472,42 @@ class UniMatch(nn.Module):
                                    num_reg_refine, pred_bidir_flow, task, intrinsics, pose, min_depth, max_depth, num_depth_candidates,
                                    depth_from_argmax, pred_bidir_depth)
 
+    _PREDICT_DEFAULTS = {'flow': (8, 'sintel', 'flow'), 'stereo': (32, 'sintel', 'disparity'), 'depth': (16, 'kitti', 'depth')}
+
+    def predict(self, img0, img1, *, inference_size=None, padding_factor=None, pad_mode=None, transpose='auto', normalize=None,
+                **forward_kw):
+        """:meth:`forward` at an inference size, with the prediction back at the images' size: the block the reference's scripts
+        repeat around the model (evaluate_flow.py:713-758, evaluate_stereo.py:340-375, evaluate_depth.py:78-129) through
+        :class:`unimatch_amd.prepost.InferenceGeometry`.  Returns the forward's dict with ``flow_preds[-1]`` restored.
+
+        ``img0``, ``img1``: fp32 ``[B, 3, H, W]`` or uint8 ``[B, H, W, 3]`` (a decoder's frames).  ``inference_size=(hp, wp)``
+        resizes (bilinear, align_corners; flow and disparity are rescaled on the way back, depth is not); ``None`` pads to multiples
+        of ``padding_factor`` as ``InputPadder(mode=pad_mode)`` does -- per task 8 / 'sintel' (flow), 32 / 'sintel' (stereo), 16 /
+        'kitti' (depth) unless given.  ``transpose='auto'`` transposes tall flow inputs and nothing else (a stereo pair or a posed
+        pair has no transposed meaning); the flow channels are not swapped back, as in the reference.  ``normalize``: ``None``
+        means ``task != 'flow'`` for uint8 input (the ImageNet constants) and ``False`` for fp32 input, which the stereo and depth
+        loaders have normalised already; flow is always normalised inside the model.  ``forward_kw`` goes to :meth:`forward`.
+        On the GPU this adds three launches to the forward and never waits for the device."""
+        from .prepost import InferenceGeometry, geometry_for, image_size
+        task = forward_kw.get('task', 'flow')
+        if task not in self._PREDICT_DEFAULTS:
+            raise ValueError(f'task must be one of {sorted(self._PREDICT_DEFAULTS)}, got {task!r}')
+        factor, mode, kind = self._PREDICT_DEFAULTS[task]
+        shape = image_size(img0)
+        if image_size(img1) != shape or img1.dtype != img0.dtype:
+            raise ValueError(f'img0 {tuple(img0.shape)} {img0.dtype} and img1 {tuple(img1.shape)} {img1.dtype} differ')
+        if isinstance(transpose, str):
+            transpose = InferenceGeometry._resolve_transpose(shape, transpose) and task == 'flow'
+        geom = geometry_for(shape, inference_size, padding_factor or factor, pad_mode or mode, transpose)
+        if normalize is None:
+            normalize = img0.dtype == torch.uint8 and task != 'flow'
+        a0, a1 = geom.prepare(img0, img1, normalize=normalize)
+        out = dict(self(a0, a1, **forward_kw))
+        preds = list(out['flow_preds'])
+        preds[-1] = geom.restore(preds[-1], kind)
+        out['flow_preds'] = preds
+        return out
+
     def _forward_batch(self, img0, img1, parts, attn_type=None, attn_splits_list=None, corr_radius_list=None,
                        prop_radius_list=None, num_reg_refine=1, pred_bidir_flow=False, task='flow', intrinsics=None,
                        pose=None, min_depth=1. / 0.5, max_depth=1. / 10, num_depth_candidates=64,

@@ -515,6 +515,65 @@ class HipOps(WorkspaceRegistry):
         _abi.check(code, 'um_flow_to_rgb')
         return rgb
 
+    # ------------------------------------------------------------------ inference-size handling
+    @staticmethod
+    def _check_sizing(name, mode, size, crop):
+        if mode not in ('pad', 'resize'):
+            raise ValueError(f"{name}: mode must be 'pad' or 'resize', got {mode!r}")
+        (hp, wp), (top, left) = (int(s) for s in size), (int(c) for c in crop)
+        if hp < 1 or wp < 1:
+            raise ValueError(f'{name}: the inference size {hp}x{wp} is empty')
+        return (1 if mode == 'resize' else 0), hp, wp, top, left
+
+    def image_prepare(self, images, size, mode='pad', crop=(0, 0), transpose=False, mean=None, std=None):
+        """``um_image_prepare``: ``images`` -- fp32 ``[B, 3, H, W]`` or uint8 ``[B, H, W, 3]`` -- to the model's input ``[B, 3, hp,
+        wp]`` fp32 with ``size = (hp, wp)``: optional transpose, ``(x / 255 - mean) / std`` when ``mean`` / ``std`` (three floats each)
+        are given, then ``mode='pad'`` (replicate padding, the image at ``crop = (top, left)``) or ``'resize'`` (bilinear,
+        align_corners).  Enqueued on the current stream: no synchronisation, no copy."""
+        u8 = images.dtype == torch.uint8
+        ok = images.is_cuda and images.dim() == 4 and (u8 or images.dtype == torch.float32) and images.shape[3 if u8 else 1] == 3
+        if not ok:
+            raise ValueError(f'image_prepare: expected a CUDA float32 [B, 3, H, W] or uint8 [B, H, W, 3] tensor, got '
+                             f'{tuple(images.shape)} {images.dtype} {images.device}')
+        if (mean is None) != (std is None) or (mean is not None and (len(mean) != 3 or len(std) != 3)):
+            raise ValueError('image_prepare: mean and std are three floats each, given together')
+        m, hp, wp, top, left = self._check_sizing('image_prepare', mode, size, crop)
+        images = images.contiguous()
+        b = images.shape[0]
+        h, w = (images.shape[1:3] if u8 else images.shape[2:])
+        ih, iw = (w, h) if transpose else (h, w)
+        if m == 0 and (top < 0 or left < 0 or top + ih > hp or left + iw > wp):
+            raise ValueError(f'image_prepare: the image {ih}x{iw} at ({top}, {left}) leaves the padded size {hp}x{wp}')
+        out = torch.empty((b, 3, hp, wp), dtype=torch.float32, device=images.device)
+        fmean = (ctypes.c_float * 3)(*mean) if mean is not None else None
+        fstd = (ctypes.c_float * 3)(*std) if std is not None else None
+        code = self._launch('image_prepare', lambda: self.lib.um_image_prepare(
+            _ptr(images), 1 if u8 else 0, _ptr(out), b, h, w, int(bool(transpose)), fmean, fstd, m, hp, wp, top, left, _stream()))
+        _abi.check(code, 'um_image_prepare')
+        return out
+
+    def pred_restore(self, pred, size, mode='pad', crop=(0, 0), kind='flow', transpose=False):
+        """``um_pred_restore``: the prediction ``pred [B, C, hp, wp]`` back to the caller's frame ``size = (H, W)``: ``mode='pad'``
+        crops at ``crop = (top, left)``, ``'resize'`` resizes and rescales by ``kind`` (``'flow'``: ``u * W / wp``, ``v * H / hp``;
+        ``'disparity'``: ``* W / wp``; ``'depth'``: nothing), then the optional transpose back (flow channels are not swapped)."""
+        kinds = {'flow': 0, 'disparity': 1, 'depth': 2}
+        if kind not in kinds:
+            raise ValueError(f'pred_restore: kind must be one of {sorted(kinds)}, got {kind!r}')
+        if not (pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 4 and pred.shape[1] == (2 if kind == 'flow' else 1)):
+            raise ValueError(f"pred_restore: expected a CUDA float32 [B, {2 if kind == 'flow' else 1}, hp, wp] {kind}, got "
+                             f'{tuple(pred.shape)} {pred.dtype} {pred.device}')
+        m, h, w, top, left = self._check_sizing('pred_restore', mode, size, crop)
+        pred = pred.contiguous()
+        b, c, hp, wp = pred.shape
+        ih, iw = (w, h) if transpose else (h, w)
+        if m == 0 and (top < 0 or left < 0 or top + ih > hp or left + iw > wp):
+            raise ValueError(f'pred_restore: the crop {ih}x{iw} at ({top}, {left}) leaves the prediction {hp}x{wp}')
+        out = torch.empty((b, c, h, w), dtype=torch.float32, device=pred.device)
+        code = self._launch('pred_restore', lambda: self.lib.um_pred_restore(
+            _ptr(pred), _ptr(out), b, c, hp, wp, m, top, left, h, w, kinds[kind], int(bool(transpose)), _stream()))
+        _abi.check(code, 'um_pred_restore')
+        return out
+
     # ------------------------------------------------------------------ evaluation metrics
     @staticmethod
     def _metric_args(name, pred, gt, channels, crop, masks):

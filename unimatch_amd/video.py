@@ -124,20 +124,31 @@ def list_frames(directory):
     return sorted(glob.glob(os.path.join(directory, '*.png')) + glob.glob(os.path.join(directory, '*.jpg')))
 
 
-def read_frame(path):
+def _decode_rgb(path):
     try:
         from PIL import Image
     except ImportError as exc:  # pragma: no cover - depends on the host
         raise RuntimeError('reading frames needs PIL (python -c "import PIL" fails here)') from exc
     img = np.array(Image.open(path)).astype(np.uint8)
-    img = np.tile(img[..., None], (1, 1, 3)) if img.ndim == 2 else img[..., :3]
-    return torch.from_numpy(img).permute(2, 0, 1).float()
+    return np.tile(img[..., None], (1, 1, 3)) if img.ndim == 2 else img[..., :3]
+
+
+def read_frame(path):
+    return torch.from_numpy(_decode_rgb(path)).permute(2, 0, 1).float()
+
+
+def read_frame_u8(path):
+    """The frame as the decoder delivers it: ``[H, W, 3]`` uint8 (the values of :func:`read_frame`, a quarter of the bytes)."""
+    return torch.from_numpy(np.ascontiguousarray(_decode_rgb(path)))
 
 
 def run_directory(model, paths, out_dir, fwd_kw, padding_factor=8, inference_size=None, pred_bidir_flow=False, fwd_bwd_check=False,
-                  save_flo=False, pairs_per_launch=8, device='cuda'):
-    """``inference_flow`` over the frames ``paths`` with the sequence mode: returns the number of pairs written."""
+                  save_flo=False, pairs_per_launch=8, device='cuda', device_resize=False):
+    """``inference_flow`` over the frames ``paths`` with the sequence mode: returns the number of pairs written.  ``device_resize``:
+    upload the frames as uint8 and transpose / resize / resize back through :class:`unimatch_amd.prepost.InferenceGeometry` (one
+    launch per step) instead of an fp32 upload and torch ops; the files written have the same names and the same format."""
     from .io import write_flo, write_png8
+    from .prepost import InferenceGeometry
     if fwd_bwd_check and not pred_bidir_flow:
         raise ValueError('--fwd-bwd-check needs --pred-bidir-flow (as the reference asserts)')
     os.makedirs(out_dir, exist_ok=True)
@@ -147,18 +158,28 @@ def run_directory(model, paths, out_dir, fwd_kw, padding_factor=8, inference_siz
     while i < len(paths) - (1 if carry is None else 0):
         take = paths[i:i + step + (1 if carry is None else 0)]
         i += len(take)
-        frames = torch.stack([read_frame(p) for p in take], 0).to(device)
-        transpose = frames.shape[-2] > frames.shape[-1]                 # the model is trained with width > height
-        if transpose:
-            frames = frames.transpose(-2, -1)
-        ori = tuple(frames.shape[-2:])
-        size = tuple(inference_size) if inference_size else tuple(int(np.ceil(s / padding_factor)) * padding_factor for s in ori)
-        if size != ori:
-            frames = F.interpolate(frames, size=size, mode='bilinear', align_corners=True)
+        geom = None
+        if device_resize:
+            frames = torch.stack([read_frame_u8(p) for p in take], 0).to(device)
+            geom = (InferenceGeometry.resized(frames.shape[1:3], inference_size, transpose='auto') if inference_size else
+                    InferenceGeometry.nearest(frames.shape[1:3], padding_factor, transpose='auto'))
+            frames, = geom.prepare(frames)
+            transpose, size, ori = False, None, None                    # the geometry has done, and will undo, all of it
+        else:
+            frames = torch.stack([read_frame(p) for p in take], 0).to(device)
+            transpose = frames.shape[-2] > frames.shape[-1]             # the model is trained with width > height
+            if transpose:
+                frames = frames.transpose(-2, -1)
+            ori = tuple(frames.shape[-2:])
+            size = tuple(inference_size) if inference_size else tuple(int(np.ceil(s / padding_factor)) * padding_factor for s in ori)
+            if size != ori:
+                frames = F.interpolate(frames, size=size, mode='bilinear', align_corners=True)
         out = model.forward_sequence(frames, pred_bidir_flow=pred_bidir_flow, pairs_per_launch=step, carry=carry, **fwd_kw)
         carry = out['carry']
         flows = [out['flow']] + ([out['flow_bwd']] if pred_bidir_flow else [])
-        if size != ori:                                                 # back to the frame size, per-component scaling
+        if geom is not None:
+            flows = [geom.restore(f, 'flow') for f in flows]
+        elif size != ori:                                               # back to the frame size, per-component scaling
             flows = [F.interpolate(f, size=ori, mode='bilinear', align_corners=True) for f in flows]
             for f in flows:
                 f[:, 0] = f[:, 0] * ori[-1] / size[-1]
@@ -200,6 +221,7 @@ def main(argv=None):
                                                     'default: the seeded synthetic weights')
     ap.add_argument('--precision', default='exact', choices=['exact', 'fast'])
     ap.add_argument('--pairs-per-launch', type=int, default=8)
+    ap.add_argument('--device-resize', action='store_true', help='upload uint8 frames; transpose, resize and resize back on the device')
     args = ap.parse_args(argv)
     paths = list_frames(args.frames)
     print(f'{len(paths)} images found')
@@ -217,7 +239,7 @@ def main(argv=None):
     fwd_kw = {k: v for k, v in fk.items() if k != 'task'}
     n = run_directory(model, paths, args.out, fwd_kw, padding_factor=args.padding_factor, inference_size=args.inference_size,
                       pred_bidir_flow=args.pred_bidir_flow, fwd_bwd_check=args.fwd_bwd_check, save_flo=args.save_flo,
-                      pairs_per_launch=args.pairs_per_launch)
+                      pairs_per_launch=args.pairs_per_launch, device_resize=args.device_resize)
     print(f'{n} pairs written to {args.out}')
 
 
