@@ -356,6 +356,16 @@ int um_nhwc_instance_norm(const float* x, const float* shortcut, const void* sho
                           int batch, int pixels, int channels, float eps, int normalize, int relu, const float* conv_stats,
                           int conv_stats_parts, void* workspace, size_t workspace_bytes, int mode, void* stream);
 
+/* um_nhwc_instance_norm whose fp32 `shortcut` is a projection shortcut's RAW convolution output: its own InstanceNorm (no ReLU,
+ * unimatch/backbone.py:24-25) is computed in registers from sc_conv_stats / sc_conv_stats_parts (the per-tile statistics that
+ * convolution left) -- the value a normalisation pass of its own would have stored and this one read back, bit for bit.  The other
+ * arguments are um_nhwc_instance_norm's; normalize must be 1; workspace: um_nhwc_norm_sc_workspace_bytes(). */
+size_t um_nhwc_norm_sc_workspace_bytes(int batch, int pixels, int channels);
+int um_nhwc_instance_norm_sc(const float* x, const float* shortcut, const void* shortcut_planes, void* planes_out, float* f32_out,
+                             int batch, int pixels, int channels, float eps, int normalize, int relu, const float* conv_stats,
+                             int conv_stats_parts, void* workspace, size_t workspace_bytes, int mode, void* stream,
+                             const float* sc_conv_stats, int sc_conv_stats_parts);
+
 /* The statistics step of um_nhwc_instance_norm on its own: per-part statistics of a convolution's epilogue (conv_stats,
  * conv_stats_parts = um_conv_stats_parts() of that convolution) -> stats_out fp32 [batch][2][channels] = (mean, 1 / sqrt(var + eps)),
  * the same kernel and the same bits um_nhwc_instance_norm(conv_stats) computes internally. */
@@ -372,6 +382,22 @@ int um_conv2d_norm_supported(int hi, int wi, int cin, int cout, int kh, int kw, 
 int um_conv2d_norm_fwd(const float* x, const float* norm_stats, int norm_relu, const void* w_planes, const float* bias, float* out,
                        float* stats_out, int batch, int hi, int wi, int cin, int cout, int kh, int kw, int stride, int pad_h,
                        int pad_w, int relu, int wshift, int mode, void* stream);
+
+/* A transition block's entry in one launch (conv_entry_kernel, the generic kernel's entry variant).  The block input
+ * X = relu(norm(u) + S) of a stride-2 residual block (unimatch/backbone.py:7-36) is read only by that block's 3x3 / stride 2 / pad 1
+ * convolution and its 1x1 / stride 2 projection, which samples the centre tap of the 3x3 window.  u: the previous block's conv2 output,
+ * fp32 [batch*hi*wi][cin]; ustats: its statistics [batch][2][cin] (um_nhwc_stats_finalize); s_planes: that block's shortcut as operand
+ * planes [NS][batch*hi*wi + 1][cin].  X is built while the operand is staged, in um_nhwc_instance_norm's arithmetic, and never
+ * written; out_t = conv3x3(X) (w_planes, no bias) and out_d = conv1x1(X) + bias2 (w2_planes), fp32 [batch*ho*wo][cout], each with its
+ * per-tile statistics (stats_t / stats_d, um_conv_stats_parts() of either geometry: the same number) -- bit-identical to
+ * um_nhwc_instance_norm(u, shortcut_planes = S, relu) -> um_conv2d_fwd(3x3) and um_conv2d_fwd(1x1, bias).  Counted once as
+ * UM_V_CONV_GENERIC.  Served for the geometries um_conv2d_entry_supported() returns 1 for (3x3 / stride 2 / pad 1, cin a multiple
+ * of 32 and <= 128, at the tile widths where the path measured faster) -- a pure function of its arguments; any other geometry is
+ * an error (-2) and nothing is launched. */
+int um_conv2d_entry_supported(int hi, int wi, int cin, int cout, int kh, int kw, int stride, int pad_h, int pad_w, int mode);
+int um_conv2d_entry_fwd(const float* u, const float* ustats, const void* s_planes, const void* w_planes, const void* w2_planes,
+                        const float* bias2, float* out_t, float* out_d, float* stats_t, float* stats_d, int batch, int hi, int wi,
+                        int cin, int cout, int kh, int kw, int stride, int pad_h, int pad_w, int wshift, int mode, void* stream);
 
 /* Channels-last element-wise helpers of the refinement block (SepConvGRU, unimatch/reg_refine.py:55-76); every result is
  * written as operand planes into columns [coff, coff + channels) of a buffer [NS = 2][plane_rows][ld]:

@@ -1,7 +1,7 @@
 """Micro-benchmark of the HIP entry points at BASELINE sizes (GPU box).  Kernel time comes from the library's
 own hipEvents (um_timing_*), so split/convert pre-passes are reported separately from the main kernels.
 
-    python tools/bench_ops.py [attn] [gsv] [local] [linear] [conv] [normconv] [--iters N] [--precision exact|fast] [--quick]
+    python tools/bench_ops.py [attn] [gsv] [local] [linear] [conv] [normconv] [entryconv] [--iters N] [--precision exact|fast] [--quick]
 """
 import ctypes
 import os
@@ -60,7 +60,7 @@ def main():
     args = sys.argv[1:]
     iters = int(args[args.index('--iters') + 1]) if '--iters' in args else 10
     prec = args[args.index('--precision') + 1] if '--precision' in args else 'exact'
-    what = [a for a in args if a in ('attn', 'gsv', 'local', 'linear', 'conv', 'normconv')] or ['attn', 'gsv', 'local', 'linear', 'conv']
+    what = [a for a in args if a in ('attn', 'gsv', 'local', 'linear', 'conv', 'normconv', 'entryconv')] or ['attn', 'gsv', 'local', 'linear', 'conv']
     ops = HipOps(prec)
     lib = _abi.load()
     issued = 3.0 if prec == 'exact' else 1.0
@@ -171,6 +171,56 @@ def main():
                 print(f'normconv {tag:28s} {name:8s} norm {norm_ms:7.4f} ms + conv {conv_ms:7.4f} ms = {norm_ms + conv_ms:7.4f} ms', flush=True)
             if len(res) == 2:
                 print(f'         bitwise equal: {torch.equal(res["planes"], res["on load"])}', flush=True)
+    if 'entryconv' in what:
+        # a stride-2 block's entry at config 2 (16 images), per tile width of the generic kernel: the parent sequence (output apply of the
+        # previous block -> conv1 3x3/2 -> projection 1x1/2 -> its normalisation pass) against finalize + entry convolution, whose
+        # projection statistics the block's output apply then finalizes itself (kernel time per call from the library's own events; this
+        # table decides kEntryConv in conv.hip)
+        for (cin, cout, hh, ww, tag) in ((64, 96, 256, 384, 'layer2.0 64->96 @256x384 (NT 3)'), (96, 128, 128, 192, 'layer3.0 96->128 @128x192 (NT 4)')):
+            nb = 16
+            xin = torch.randn(nb, cin, hh, ww, device=dev, generator=g)
+            w0 = torch.randn(cin, cin, 3, 3, device=dev, generator=g) * 0.05
+            w1 = torch.randn(cout, cin, 3, 3, device=dev, generator=g) * 0.05
+            wp = torch.randn(cout, cin, 1, 1, device=dev, generator=g) * 0.1
+            bp = torch.randn(cout, device=dev, generator=g)
+            splanes, _ = ops.nchw_to_nhwc(xin, want_planes=True, want_f32=False)          # the previous block's shortcut
+            u, _, _ = ops.conv2d_nhwc((splanes, nb, hh, ww, cin), w0, None, 1, (1, 1), stats=True)
+            st = ops.last_conv_stats
+            ho, wo = (hh - 1) // 2 + 1, (ww - 1) // 2 + 1
+            del xin
+
+            def parent():
+                xp, _ = ops.nhwc_norm(u, nb, hh * ww, relu=True, shortcut_planes=splanes, want_planes=True, conv_stats=st)
+                t = ops.conv2d_nhwc((xp, nb, hh, ww, cin), w1, None, 2, (1, 1), stats=True)[0]
+                d = ops.conv2d_nhwc((xp, nb, hh, ww, cin), wp, bp, 2, (0, 0), stats=True)[0]
+                _, sc = ops.nhwc_norm(d, nb, ho * wo, relu=False, want_planes=False, want_f32=True, conv_stats=ops.last_conv_stats)
+                return t, d
+
+            def entry():
+                return ops.conv2d_entry(u, st, splanes, (nb, hh, ww, cin), w1, wp, bp)[:2]
+
+            res = {}
+            for name, fn in (('parent', parent), ('entry', entry), ('parent', parent), ('entry', entry)):
+                if name == 'entry' and not ops.conv2d_entry_supported(hh, ww, cin, w1, wp):
+                    continue
+                for _ in range(2):
+                    out = fn()
+                torch.cuda.synchronize()
+                lib.um_timing_enable(-1)
+                collect(lib)
+                for _ in range(iters):
+                    fn()
+                torch.cuda.synchronize()
+                lib.um_timing_enable(0)
+                tm = collect(lib)
+                norm_ms = tm['instance_norm'][0] * tm['instance_norm'][1] / iters
+                conv_ms = tm['conv'][0] * tm['conv'][1] / iters
+                res.setdefault(name, out)
+                print(f'entryconv {tag:34s} {name:7s} norm {norm_ms:7.4f} ms + conv {conv_ms:7.4f} ms = {norm_ms + conv_ms:7.4f} ms', flush=True)
+            if len(res) == 2:
+                print(f'          bitwise equal: t {torch.equal(res["parent"][0], res["entry"][0])}, d {torch.equal(res["parent"][1], res["entry"][1])}',
+                      flush=True)
+            del splanes, u
     if 'conv' in what:
         # refinement-block convolutions at config 4 (4 pairs @ 1/4 resolution = 128 x 192)
         nb, hh, ww = 4, 128, 192

@@ -57,6 +57,11 @@ SIGNATURES = {
                                         _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, ctypes.c_long] + [_c_int] * 11 + [_c_void_p]),
     'um_conv2d_norm_supported': (_c_int, [_c_int] * 10),
     'um_conv2d_norm_fwd': (_c_int, [_c_void_p, _c_void_p, _c_int] + [_c_void_p] * 4 + [_c_int] * 13 + [_c_void_p]),
+    'um_conv2d_entry_supported': (_c_int, [_c_int] * 10),
+    'um_conv2d_entry_fwd': (_c_int, [_c_void_p] * 10 + [_c_int] * 12 + [_c_void_p]),
+    'um_nhwc_norm_sc_workspace_bytes': (_c_size_t, [_c_int] * 3),
+    'um_nhwc_instance_norm_sc': (_c_int, [_c_void_p] * 5 + [_c_int] * 3 + [ctypes.c_float, _c_int, _c_int, _c_void_p, _c_int, _c_void_p,
+                                          _c_size_t, _c_int, _c_void_p, _c_void_p, _c_int]),
     'um_nhwc_stats_finalize': (_c_int, [_c_void_p, _c_int, _c_void_p] + [_c_int] * 3 + [ctypes.c_float, _c_void_p]),
     'um_conv_stats_bytes': (_c_size_t, [_c_int] * 3),
     'um_conv_stats_parts': (_c_int, [_c_int] * 8),

@@ -4,6 +4,7 @@ In-tree on purpose: the built ``.so`` travels with a snapshot of the repository 
 history stays source-only).  hipcc cross-compiles without a GPU.  Usage: ``python -m unimatch_amd.build``.
 """
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -25,6 +26,10 @@ EXTRA_FLAGS = {'ffn.hip': ['-fno-slp-vectorize'], 'global_match.hip': ['-fno-slp
                'metrics.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
                # the resize / normalise kernels are compared bit for bit with a host restatement of the same operation order
                'prepost.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt']}
+# kernels that sit at the register limit of their occupancy (conv_entry_kernel<Fp16, 2, 4>: all 256 VGPRs of two workgroups per CU): the
+# build reads the compiler's resource report for these sources and fails if a named kernel spills to scratch or loses occupancy,
+# instead of shipping a silently slower kernel.  source -> {substring of the mangled kernel name: minimum waves per SIMD}
+RESOURCE_GUARDS = {'conv.hip': {'conv_entry_kernel': 2}}
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result']
 
 
@@ -33,6 +38,32 @@ def find_hipcc():
         if cand and os.path.exists(cand):
             return cand
     raise RuntimeError('hipcc not found: the HIP extension cannot be built')
+
+
+def parse_resource_report(text):
+    """``-Rpass-analysis=kernel-resource-usage`` remarks -> ``{mangled kernel name: {'VGPRs': n, 'ScratchSize': n, 'Occupancy': n, ...}}``."""
+    out, cur = {}, None
+    for line in text.splitlines():
+        m = re.search(r'remark: .*?Function Name: (\S+)', line)
+        if m:
+            cur = out.setdefault(m.group(1), {})
+            continue
+        m = re.search(r'remark: .*?\s{2,}([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)', line)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = int(m.group(2))
+    return out
+
+
+def check_resources(src, report):
+    """Raise when a guarded kernel of ``src`` (RESOURCE_GUARDS) is missing from the report, uses scratch or is below its occupancy."""
+    for key, min_occ in RESOURCE_GUARDS.get(src, {}).items():
+        hits = {k: v for k, v in report.items() if key in k}
+        if not hits:
+            raise RuntimeError(f'{src}: no resource report for {key}: the guard of unimatch_amd/build.py has nothing to check')
+        for name, r in hits.items():
+            if r.get('ScratchSize', -1) != 0 or r.get('Occupancy', 0) < min_occ:
+                raise RuntimeError(f'{src}: {name} needs scratch {r.get("ScratchSize")} B/lane at occupancy {r.get("Occupancy")} '
+                                   f'({r.get("VGPRs")} VGPRs): it was written for no scratch at {min_occ} waves per SIMD')
 
 
 def _stale(target, deps):
@@ -52,11 +83,26 @@ def build(force=False, verbose=False):
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace('.hip', '.o'))
-        if force or _stale(o, [s] + hdrs):
+        # a guarded source's report is part of its build: an object without one (built before the guard, or cleaned) is compiled again
+        if force or _stale(o, [s] + hdrs) or (src in RESOURCE_GUARDS and not os.path.exists(o[:-2] + '.resources.txt')):
             cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + ['-c', s, '-o', o]
             if verbose:
                 print(' '.join(cmd))
-            subprocess.run(cmd, check=True, cwd=CSRC)
+            if src in RESOURCE_GUARDS:
+                done = subprocess.run(cmd + ['-Rpass-analysis=kernel-resource-usage', '-fno-caret-diagnostics'], cwd=CSRC, stderr=subprocess.PIPE, text=True)
+                remarks = [ln for ln in done.stderr.splitlines() if 'kernel-resource-usage' in ln]
+                sys.stderr.write('\n'.join(ln for ln in done.stderr.splitlines() if 'kernel-resource-usage' not in ln))
+                if done.returncode != 0:
+                    raise subprocess.CalledProcessError(done.returncode, cmd)
+                try:
+                    check_resources(src, parse_resource_report('\n'.join(remarks)))
+                except RuntimeError:
+                    os.remove(o)                     # not a usable object: the next build must compile (and check) it again
+                    raise
+                with open(o[:-2] + '.resources.txt', 'w') as f:
+                    f.write('\n'.join(remarks) + '\n')
+            else:
+                subprocess.run(cmd, check=True, cwd=CSRC)
         objs.append(o)
     if force or _stale(LIB, objs):
         cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB] + objs + ['-ldl']

@@ -18,7 +18,8 @@
 // computed transposed (D^T = W . A^T) so that lane = pixel.  Output: fp32 NHWC and / or the next convolution's operand
 // planes (+ bias, activation, SepConvGRU gates, InstanceNorm statistics), see conv_epilogue.
 //
-// Three kernels share the operand format and the epilogue; conv_pick() chooses:
+// Three kernels share the operand format and the epilogue; conv_pick() chooses (conv_entry_kernel, the generic kernel's variant for a
+// stride-2 residual block's first convolution + projection, has its own entry point: um_conv2d_entry_fwd):
 //   conv_kernel        any geometry (strides, 1x1, 5x1, 7x7 via um_conv7_fwd): one staged tile per tap and 32-channel chunk
 //   conv_rows_kernel   same-size stride-1 rows of 3 / 5 taps: one 256-pixel window per kernel row serves its KW taps
 //   conv_patch_kernel  3x3 / stride 1 / pad 1: an 8 x 32 pixel tile whose halo patch is staged once per 16-channel chunk for
@@ -326,15 +327,47 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[N
                                                               lane, half);
 }
 
-template <typename T, int NS, int NT>
-__global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
-    constexpr int TILE = 128 * 64;               // one 128-row x 64-byte operand tile (one plane, one stage)
-    constexpr int WTILE = 32 * NT * 64;          // one weight plane of a stage: 32 NT output rows x 64 bytes
-    constexpr int STAGE = NS * (TILE + WTILE);   // activation planes then weight planes (NT = 2: 48 KB ring -> 3 WG / CU)
-    constexpr int EPI = 4 * 32 * (32 * NT * 4);   // the epilogue's transposed tile
-    constexpr int RING = (2 * STAGE > EPI) ? 2 * STAGE : EPI;
+// ---- entry variant of the generic kernel (conv_entry_kernel): a transition block's first convolution, 3x3 / stride 2 / pad 1 ----
+// The block input X = relu(norm(u) + S) has two readers only, both at stride 2: this convolution and the block's 1x1 projection
+// shortcut, which samples pixel (2i, 2j) = the centre tap of output (i, j).  So X is never written: the activation tile of a stage
+// is built in registers from u (the previous block's conv2 output, fp32 NHWC), its finalized statistics (mean, rstd) and that
+// block's shortcut planes S, with um_norm_value8 -- nhwc_apply_kernel's arithmetic, bit for bit the planes that kernel writes --
+// and stored where the LDS-DMA would have put it (same swizzle).  Out-of-image taps are zeroed AFTER the normalisation (norm(0) != 0).
+// The loads run one stage ahead in registers; the weight tiles keep their LDS-DMA path; the statistics of the image sit in LDS.
+// During the stages of the centre tap the staged tile is also multiplied with the projection's 1x1 weights into a second
+// accumulator set, in the cc / ks / product order of the stand-alone 1x1 launch (whose K axis is exactly these stages): d is
+// bitwise that launch's output.  Its weight fragments come straight from global memory (L2: all workgroups read the same
+// [Cout][Cin] planes) half a stage ahead -- the ring has no room for a third tile at two workgroups per CU.  Two epilogues: t (no
+// bias) and d (+ the projection's bias), each with its per-tile statistics in the same 128-pixel tile numbering.
+struct ConvEntryArgs {
+    const float* u;               // [B*Hi*Wi][Cin] fp32
+    const float* ustats;          // [B][2][Cin] (mean, rstd) of u
+    const unsigned short* sp;     // shortcut planes [NS][B*Hi*Wi + 1][Cin]
+    long s_plane_stride;
+    const unsigned short* wp2;    // projection weights [NS][Cout][Cin]
+    long w2_plane_stride;
+    const float* bias2;           // [Cout]
+    float* out2;                  // d: fp32 [M][Cout]
+    float* stats2;                // [M / 128][3][Cout]
+};
+
+template <int NS, int NT>
+struct ConvLds {
+    static constexpr int TILE = 128 * 64;               // one 128-row x 64-byte operand tile (one plane, one stage)
+    static constexpr int WTILE = 32 * NT * 64;          // one weight plane of a stage: 32 NT output rows x 64 bytes
+    static constexpr int STAGE = NS * (TILE + WTILE);   // activation planes then weight planes (NT = 2: 48 KB ring -> 3 WG / CU)
+    static constexpr int EPI = 4 * 32 * (32 * NT * 4);   // the epilogue's transposed tile
+    static constexpr int RING = (2 * STAGE > EPI) ? 2 * STAGE : EPI;
     // + per-wave (mean, M2) columns at the stride of 8 waves + per-wave pixel counts (the epilogue's scratch layout)
-    __shared__ __attribute__((aligned(16))) unsigned char lds[RING + 8 * 2 * 32 * NT * 4 + 64];
+    static constexpr int TOTAL = RING + 8 * 2 * 32 * NT * 4 + 64;
+    static constexpr int ENTRY_CIN = 128;               // entry variant: (mean, rstd) of up to 128 input channels behind the scratch
+    static constexpr int ENTRY_TOTAL = TOTAL + 2 * ENTRY_CIN * 4;
+};
+
+template <typename T, int NS, int NT, bool ENTRY>
+__device__ __forceinline__ void conv_body(const ConvArgs& a, const ConvEntryArgs& e, unsigned char* lds) {
+    using L = ConvLds<NS, NT>;
+    constexpr int TILE = L::TILE, WTILE = L::WTILE, STAGE = L::STAGE, RING = L::RING;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -366,26 +399,32 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
         pbase[i] = bt * a.Hi * a.Wi;
     }
     const unsigned zero_row = a.zero_row;
-    unsigned rowoff[2];                          // byte offset of the source row of the tap being staged
+    unsigned rowoff[2];                          // byte offset of the source row of the tap being staged (ENTRY: the row index, ~0 = none)
     auto set_tap = [&](int ky, int kx) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int iy = py[i] + ky, ix = px[i] + kx;
             const bool ok = pok[i] && (unsigned)iy < (unsigned)a.Hi && (unsigned)ix < (unsigned)a.Wi;
-            const unsigned row = ok ? (unsigned)(pbase[i] + iy * a.Wi + ix) : zero_row;
-            rowoff[i] = row * a.row_stride;
+            if constexpr (ENTRY) {
+                rowoff[i] = ok ? (unsigned)(pbase[i] + iy * a.Wi + ix) : ~0u;
+            } else {
+                const unsigned row = ok ? (unsigned)(pbase[i] + iy * a.Wi + ix) : zero_row;
+                rowoff[i] = row * a.row_stride;
+            }
         }
     };
     int ky = 0, kx = 0, cc = 0;                  // position of the NEXT stage to be issued
     // 16-byte chunk cp of row r holds source chunk cp ^ ((r >> 2) & 3) (conflict-free ds_read_b128 fragments)
     auto stage_async = [&](int c0, int kglob, unsigned char* buf) {
+        if constexpr (!ENTRY) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int r = 32 * wave + 16 * i + (lane >> 2);
-            const int sc = dcp ^ ((r >> 2) & 3);
-            const unsigned off = rowoff[i] + (unsigned)((c0 + 8 * sc) * 2);
+            for (int i = 0; i < 2; ++i) {
+                const int r = 32 * wave + 16 * i + (lane >> 2);
+                const int sc = dcp ^ ((r >> 2) & 3);
+                const unsigned off = rowoff[i] + (unsigned)((c0 + 8 * sc) * 2);
 #pragma unroll
-            for (int pl = 0; pl < NS; ++pl) conv_dma16(a.ap + pl * a.a_plane_stride, off, buf + pl * TILE + (32 * wave + 16 * i) * 64);
+                for (int pl = 0; pl < NS; ++pl) conv_dma16(a.ap + pl * a.a_plane_stride, off, buf + pl * TILE + (32 * wave + 16 * i) * 64);
+            }
         }
         // the weight tile is 2 NT blocks of 16 rows; block j goes to wave j mod 4 (every wave issues its share)
 #pragma unroll
@@ -402,12 +441,75 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
             }
         }
     };
+    // ---- ENTRY operand path: item i = the 8 channels c0 + 8 esc of the lane's row i, held in registers for one stage
+    const int esc = dcp ^ ((lane >> 4) & 3);                      // = sc of stage_async (bits 2..3 of the row are bits 4..5 of the lane)
+    float* sstat = reinterpret_cast<float*>(lds + L::TOTAL);      // ENTRY: (mean | rstd) of image bt, [2][Cin]
+    f32x4 eu[2][2];
+    u32x4 esh[2], esl[2];
+    bool eok[2];
+    int ec0 = 0;
+    auto entry_load = [&](int c0) {
+        ec0 = c0 + 8 * esc;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            eok[i] = rowoff[i] != ~0u;
+            const unsigned el = (eok[i] ? rowoff[i] : 0u) * (unsigned)a.Cin + (unsigned)ec0;      // (not image: any valid pixel)
+            const unsigned char* pu = reinterpret_cast<const unsigned char*>(e.u) + el * 4u;
+            eu[i][0] = *reinterpret_cast<const f32x4*>(pu);       // ordinary loads: the other taps re-read the pixel through L2
+            eu[i][1] = *reinterpret_cast<const f32x4*>(pu + 16);
+            const unsigned char* ps = reinterpret_cast<const unsigned char*>(e.sp) + el * 2u;
+            esh[i] = *reinterpret_cast<const u32x4*>(ps);
+            if (NS == 2) esl[i] = *reinterpret_cast<const u32x4*>(ps + e.s_plane_stride * 2);
+        }
+    };
+    auto entry_store = [&](unsigned char* buf) {
+        float mu[8], rs[8];
+        {
+            const f32x4 m0 = *reinterpret_cast<const f32x4*>(sstat + ec0), m1 = *reinterpret_cast<const f32x4*>(sstat + ec0 + 4);
+            const f32x4 r0 = *reinterpret_cast<const f32x4*>(sstat + a.Cin + ec0), r1 = *reinterpret_cast<const f32x4*>(sstat + a.Cin + ec0 + 4);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                mu[k] = m0[k];
+                mu[4 + k] = m1[k];
+                rs[k] = r0[k];
+                rs[4 + k] = r1[k];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float v[8], none[8];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                v[k] = eu[i][0][k];
+                v[4 + k] = eu[i][1][k];
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) none[k] = 0.f;
+            u32x4 h, l = {0u, 0u, 0u, 0u};
+            um_norm_value8<T, NS>(v, true, mu, rs, true, 2, none, false, none, none, esh[i], NS == 2 ? esl[i] : l, true, h, l);
+            unsigned char* dst = buf + (32 * wave + 16 * i) * 64 + lane * 16;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                h[k] = eok[i] ? h[k] : 0u;
+                l[k] = eok[i] ? l[k] : 0u;
+            }
+            *reinterpret_cast<u32x4*>(dst) = h;
+            if (NS == 2) *reinterpret_cast<u32x4*>(dst + TILE) = l;
+        }
+    };
 
     f32x16 acc[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
+    f32x16 acc2[ENTRY ? NT : 1];                 // ENTRY: the projection's accumulators
+    if constexpr (ENTRY) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc2[nt][r] = 0.f;
+    }
 
     // fragment offsets inside a tile: row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4), chunk = 2 * kstep + half
     const int fr = lane & 31;
@@ -415,9 +517,25 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) foff[ks] = fr * 64 + (((2 * ks + half) ^ ((fr >> 2) & 3)) << 4);
 
+    // ENTRY: the projection's weight fragments of one k-step (rows n0 + 32 nt + fr, 8 channels), from global memory
+    i16x8 pwh[ENTRY ? NT : 1], pwl[ENTRY ? NT : 1];
+    auto proj_load = [&](int pcc, int ks) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int n = min(n0 + 32 * nt + fr, a.Cout - 1);
+            const unsigned short* pw = e.wp2 + (unsigned)(n * a.Cin + pcc * 32 + (2 * ks + half) * 8);
+            pwh[nt] = *reinterpret_cast<const i16x8*>(pw);
+            if (NS == 2) pwl[nt] = *reinterpret_cast<const i16x8*>(pw + e.w2_plane_stride);
+        }
+    };
+
     // ---- prologue: stage 0 ------------------------------------------------------------------------------------
     set_tap(0, 0);
     stage_async(0, 0, lds);
+    if constexpr (ENTRY) {
+        entry_load(0);
+        for (int k = tid; k < 2 * a.Cin; k += 256) sstat[k] = e.ustats[(long)bt * 2 * a.Cin + k];
+    }
     auto advance = [&]() {                       // move (ky, kx, cc) one stage on; recompute the row offsets on a new tap
         if (++cc == cpt) {
             cc = 0;
@@ -429,14 +547,24 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
         }
     };
     advance();
+    if constexpr (ENTRY) {
+        __syncthreads();                         // the statistics
+        entry_store(lds);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
+    int ptap = 0, pcc = 0;                       // ENTRY: tap and chunk of the stage being multiplied
     for (int s = 0; s < nstage; ++s) {
         unsigned char* cur = lds + (s & 1) * STAGE;
         unsigned char* nxt = lds + ((s & 1) ^ 1) * STAGE;
+        const bool centre = ENTRY && ptap == 4;                   // (ky, kx) = (1, 1)
+        if constexpr (ENTRY) {
+            if (centre) proj_load(pcc, 0);
+        }
         if (s + 1 < nstage) {
             stage_async(cc * 32, (s + 1) * 32, nxt);
+            if constexpr (ENTRY) entry_load(cc * 32);
             advance();
         }
         const unsigned char* at = cur + 32 * wave * 64;           // this wave's 32 pixel rows
@@ -457,8 +585,28 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
                 }
                 acc[nt] = T::mfma(wh, bh, acc[nt]);
             }
+            if constexpr (ENTRY) {
+                if (centre) {
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) {
+                        if (NS == 2) {
+                            if (UM_CONV_2P != 1) acc2[nt] = T::mfma(pwl[nt], bh, acc2[nt]);
+                            if (UM_CONV_2P != 2) acc2[nt] = T::mfma(pwh[nt], bl, acc2[nt]);
+                        }
+                        acc2[nt] = T::mfma(pwh[nt], bh, acc2[nt]);
+                    }
+                    if (ks == 0) proj_load(pcc, 1);
+                }
+            }
         }
         __builtin_amdgcn_s_setprio(0);
+        if constexpr (ENTRY) {
+            if (s + 1 < nstage) entry_store(nxt);
+            if (++pcc == cpt) {
+                pcc = 0;
+                ++ptap;
+            }
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
@@ -467,7 +615,30 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
         const int rloc0 = pl0 + 32 * wave;
         conv_epilogue<T, NS, NT>(a, acc, lds, lds + RING, bt, rloc0, min(32, max(0, P - rloc0)), bt * ((P + 127) / 128) + pl0 / 128, false,
                                  n0, tid, wave, lane, half);
+        if constexpr (ENTRY) {
+            ConvArgs a2 = a;
+            a2.bias = e.bias2;
+            a2.out = e.out2;
+            a2.stats = e.stats2;
+            __syncthreads();                     // the first epilogue's statistics scratch has been read
+            conv_epilogue<T, NS, NT>(a2, acc2, lds, lds + RING, bt, rloc0, min(32, max(0, P - rloc0)), bt * ((P + 127) / 128) + pl0 / 128,
+                                     false, n0, tid, wave, lane, half);
+        }
     }
+}
+
+template <typename T, int NS, int NT>
+__global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[ConvLds<NS, NT>::TOTAL];
+    conv_body<T, NS, NT, false>(a, ConvEntryArgs{}, lds);
+}
+
+// <Fp16, 2, 4> uses all 256 VGPRs of two workgroups per CU without scratch: anything added to the main loop spills.  The build reads
+// the compiler's resource report for this kernel and fails on scratch or lost occupancy (RESOURCE_GUARDS in unimatch_amd/build.py).
+template <typename T, int NS, int NT>
+__global__ __launch_bounds__(256, 2) void conv_entry_kernel(ConvArgs a, ConvEntryArgs e) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[ConvLds<NS, NT>::ENTRY_TOTAL];
+    conv_body<T, NS, NT, true>(a, e, lds);
 }
 
 // ---- row-window variant: same-size stride-1 convolutions with KW = 3 / 5 horizontal taps -------------------------------------
@@ -947,6 +1118,18 @@ static hipError_t launch_conv(const ConvArgs& a, int mode, hipStream_t stream) {
     return hipGetLastError();
 }
 
+template <int NT>
+static hipError_t launch_conv_entry(const ConvArgs& a, const ConvEntryArgs& e, int mode, hipStream_t stream) {
+    dim3 grid(a.B * ((a.Ho * a.Wo + 127) / 128) * ((a.Cout + 32 * NT - 1) / (32 * NT))), block(256);
+    ScopedKernelTimer timer(UM_K_CONV, stream);
+    um_census_hit(UM_V_CONV_GENERIC);                             // one launch of the generic tiling (it also is the projection)
+    if (mode == 0)
+        hipLaunchKernelGGL((conv_entry_kernel<Fp16, 2, NT>), grid, block, 0, stream, a, e);
+    else
+        hipLaunchKernelGGL((conv_entry_kernel<Bf16, 1, NT>), grid, block, 0, stream, a, e);
+    return hipGetLastError();
+}
+
 template <int NT, int KW, int NSLOT>
 static hipError_t launch_conv_rows(const ConvArgs& a, int mode, hipStream_t stream) {
     static bool configured[2] = {false, false};    // opt in to > 64 KB of LDS once per instantiation
@@ -1049,6 +1232,22 @@ extern "C" int um_conv2d_norm_supported(int hi, int wi, int cin, int cout, int k
     int nt;
     if (conv_pick(hi, wi, ho, wo, cout, kh, kw, stride, pad_h, pad_w, &nt) != CONV_PATCH) return 0;
     return nt >= 2 && nt <= 4 && kNormOnLoad[nt] ? 1 : 0;
+}
+
+// ---- the entry variant (conv_entry_kernel): which tile widths of the generic kernel take it.  Decided per width by measurement on
+// MI355X (profiles/entry_conv_ab.txt: finalize + entry convolution against apply + conv1 + projection + its normalisation pass at
+// the encoder's two transition shapes); a width that lost stays on the parent sequence.  NT = 3 serves 64 -> 96, NT = 4 96 -> 128.
+static constexpr bool kEntryConv[5] = {false, false, false, true, true};       // index = NT
+
+extern "C" int um_conv2d_entry_supported(int hi, int wi, int cin, int cout, int kh, int kw, int stride, int pad_h, int pad_w, int mode) {
+    if (hi <= 0 || wi <= 0 || cin <= 0 || cin % 32 != 0 || cin > ConvLds<2, 4>::ENTRY_CIN || cout <= 0 || cout % 4 != 0 ||
+        (mode != 0 && mode != 1))
+        return 0;
+    if (kh != 3 || kw != 3 || stride != 2 || pad_h != 1 || pad_w != 1) return 0;      // a transition block's first convolution
+    const int ho = (hi - 1) / 2 + 1, wo = (wi - 1) / 2 + 1;
+    int nt;
+    if (conv_pick(hi, wi, ho, wo, cout, 3, 3, 2, 1, 1, &nt) != CONV_GENERIC) return 0;
+    return nt >= 3 && nt <= 4 && kEntryConv[nt] ? 1 : 0;
 }
 
 extern "C" int um_conv_stats_parts(int hi, int wi, int cout, int kh, int kw, int stride, int pad_h, int pad_w) {
@@ -1258,6 +1457,75 @@ extern "C" int um_conv2d_norm_fwd(const float* x, const float* norm_stats, int n
     return conv2d_impl(nullptr, cin, 0, rows_in + 1, w_planes, bias, out, cout, 0, nullptr, 0, 0, 0, stats_out, batch, hi, wi, cin, cout, kh,
                        kw, stride, pad_h, pad_w, relu ? 1 : 0, wshift, mode, stream_, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, x,
                        norm_stats, norm_relu ? 1 : 0);
+}
+
+// A transition block's entry in one launch: t = conv3x3/2(X) and d = conv1x1/2(X) + bias2 with X = relu(norm(u) + S) built while the
+// operand is staged (conv_entry_kernel).  u: fp32 [batch*hi*wi][cin], ustats: its finalized statistics [batch][2][cin]
+// (um_nhwc_stats_finalize), s_planes: the shortcut as operand planes [NS][batch*hi*wi + 1][cin].  Bit-identical to
+// um_nhwc_instance_norm(u, shortcut_planes, relu) -> um_conv2d_fwd(3x3, stats) + um_conv2d_fwd(1x1, bias, stats).
+extern "C" int um_conv2d_entry_fwd(const float* u, const float* ustats, const void* s_planes, const void* w_planes, const void* w2_planes,
+                                   const float* bias2, float* out_t, float* out_d, float* stats_t, float* stats_d, int batch, int hi, int wi,
+                                   int cin, int cout, int kh, int kw, int stride, int pad_h, int pad_w, int wshift, int mode, void* stream_) {
+    if (!u || !ustats || !s_planes || !w_planes || !w2_planes || !out_t || !out_d || batch <= 0 || wshift < 0 || wshift > 14) {
+        um_set_error("um_conv2d_entry_fwd: bad argument (a null input / output, batch=%d, wshift=%d)", batch, wshift);
+        return -1;
+    }
+    if (!um_conv2d_entry_supported(hi, wi, cin, cout, kh, kw, stride, pad_h, pad_w, mode)) {
+        um_set_error("um_conv2d_entry_fwd: no entry kernel for this geometry (hi=%d wi=%d cin=%d cout=%d k=%dx%d stride=%d pad=%d,%d mode=%d): "
+                     "ask um_conv2d_entry_supported() first", hi, wi, cin, cout, kh, kw, stride, pad_h, pad_w, mode);
+        return -2;
+    }
+    if ((((unsigned long)u | (unsigned long)s_planes | (unsigned long)w_planes | (unsigned long)w2_planes | (unsigned long)bias2 |
+          (unsigned long)out_t | (unsigned long)out_d) & 15) != 0 || (((unsigned long)ustats | (unsigned long)stats_t | (unsigned long)stats_d) & 3) != 0) {
+        um_set_error("um_conv2d_entry_fwd: inputs, planes, bias and outputs must be 16-byte aligned");
+        return -1;
+    }
+    const int ho = (hi - 1) / 2 + 1, wo = (wi - 1) / 2 + 1;
+    const long rows_in = (long)batch * hi * wi, m = (long)batch * ho * wo;
+    if (rows_in * cin * 4 >= (1L << 32) - 1 || (long)cout * 9 * cin * 2 >= (1L << 32) || m >= (1L << 31)) {
+        um_set_error("um_conv2d_entry_fwd: an input beyond 4 GiB is not addressable by this kernel");
+        return -4;
+    }
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.wp = (const unsigned short*)w_planes;
+    a.w_plane_stride = (long)cout * 9 * cin;
+    a.out = out_t;
+    a.out_ld = cout;
+    a.stats = stats_t;
+    a.B = batch;
+    a.Hi = hi;
+    a.Wi = wi;
+    a.Cin = cin;
+    a.Ho = ho;
+    a.Wo = wo;
+    a.Cout = cout;
+    a.KH = a.KW = 3;
+    a.stride = 2;
+    a.pad_h = a.pad_w = 1;
+    a.M = (int)m;
+    a.gate_c = cout;
+    a.out_scale = ldexpf(1.f, -wshift);
+    a.xcd = conv_xcd_enabled();
+    ConvEntryArgs e;
+    e.u = u;
+    e.ustats = ustats;
+    e.sp = (const unsigned short*)s_planes;
+    e.s_plane_stride = (rows_in + 1) * cin;
+    e.wp2 = (const unsigned short*)w2_planes;
+    e.w2_plane_stride = (long)cout * cin;
+    e.bias2 = bias2;
+    e.out2 = out_d;
+    e.stats2 = stats_d;
+    int nt;
+    conv_pick(hi, wi, ho, wo, cout, 3, 3, 2, 1, 1, &nt);
+    hipStream_t st = (hipStream_t)stream_;
+    const hipError_t err = nt == 3 ? launch_conv_entry<3>(a, e, mode, st) : launch_conv_entry<4>(a, e, mode, st);
+    if (err != hipSuccess) {
+        um_set_error("um_conv2d_entry_fwd: launch failed: %s", hipGetErrorString(err));
+        return (int)err;
+    }
+    return 0;
 }
 
 // ---- 7x7 convolutions with very few input channels on the same kernel ----------------------------------------------------

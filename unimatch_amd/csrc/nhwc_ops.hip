@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void nhwc_stats_finalize_kernel(const float* p
 //   y = relu(shortcut + y)         if shortcut (fp32) or shortcut_planes (operand planes of the same shape, hi + lo: what the
 //                                  block's first convolution read -- the identity shortcut then needs no fp32 copy in HBM)
 template <typename T, int NS>
-__global__ __launch_bounds__(256) void nhwc_apply_kernel(const float* x, const float* stats, const float* shortcut,
+__global__ __launch_bounds__(256) void nhwc_apply_kernel(const float* x, const float* stats, const float* shortcut, const float* sc_stats,
                                                          const unsigned short* shortcut_planes, unsigned short* planes,
                                                          float* outf, long rows, int P, int C, int relu) {
     const int c8n = C >> 3;
@@ -169,7 +169,9 @@ __global__ __launch_bounds__(256) void nhwc_apply_kernel(const float* x, const f
         for (int pl = 0; pl < NS; ++pl) *reinterpret_cast<u32x4*>(planes + pl * plane_stride + row * C + c) = z;
         return;
     }
-    float v[8];
+    float v[8], mu[8], rs[8], s[8], smu[8], srs[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) mu[i] = rs[i] = s[i] = smu[i] = srs[i] = 0.f;
     {
         // x is read exactly once: streaming loads (the output planes are re-read by the next convolution: ordinary stores)
         const f32x4 a0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + row * C + c));
@@ -180,54 +182,46 @@ __global__ __launch_bounds__(256) void nhwc_apply_kernel(const float* x, const f
             v[4 + i] = a1[i];
         }
     }
+    const int b = (int)(row / P);
     if (stats) {
-        const int b = (int)(row / P);
-        const float* mu = stats + ((long)b * 2) * C + c;
-        const float* rs = mu + C;
+        const float* m = stats + ((long)b * 2) * C + c;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = (v[i] - mu[i]) * rs[i];
+        for (int i = 0; i < 8; ++i) {
+            mu[i] = m[i];
+            rs[i] = m[C + i];
+        }
     }
-    if (relu) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = fmaxf(v[i], 0.f);
-    }
+    u32x4 sh = {0u, 0u, 0u, 0u}, sl = sh;
     if (shortcut) {
         const f32x4 s0 = *reinterpret_cast<const f32x4*>(shortcut + row * C + c);
         const f32x4 s1 = *reinterpret_cast<const f32x4*>(shortcut + row * C + c + 4);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            v[i] = fmaxf(v[i] + s0[i], 0.f);
-            v[4 + i] = fmaxf(v[4 + i] + s1[i], 0.f);
+            s[i] = s0[i];
+            s[4 + i] = s1[i];
+        }
+        if (sc_stats) {                                           // the projection shortcut's own InstanceNorm (no ReLU), in registers
+            const float* m = sc_stats + ((long)b * 2) * C + c;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                smu[i] = m[i];
+                srs[i] = m[C + i];
+            }
         }
     } else if (shortcut_planes) {
-        const u32x4 sh = *reinterpret_cast<const u32x4*>(shortcut_planes + row * C + c);
-        u32x4 sl = {0u, 0u, 0u, 0u};
+        sh = *reinterpret_cast<const u32x4*>(shortcut_planes + row * C + c);
         if (NS == 2) sl = *reinterpret_cast<const u32x4*>(shortcut_planes + plane_stride + row * C + c);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const f32x2 uh = T::unpack2(sh[i]);
-            f32x2 ul = {0.f, 0.f};
-            if (NS == 2) ul = T::unpack2(sl[i]);
-            v[2 * i] = fmaxf(v[2 * i] + (uh[0] + ul[0]), 0.f);
-            v[2 * i + 1] = fmaxf(v[2 * i + 1] + (uh[1] + ul[1]), 0.f);
-        }
     }
+    u32x4 h, l;
+    um_norm_value8<T, NS>(v, stats != nullptr, mu, rs, relu != 0, shortcut ? 1 : shortcut_planes ? 2 : 0, s, sc_stats != nullptr, smu, srs,
+                          sh, sl, planes != nullptr, h, l);
     if (outf) {
         *reinterpret_cast<f32x4*>(outf + row * C + c) = f32x4{v[0], v[1], v[2], v[3]};
         *reinterpret_cast<f32x4*>(outf + row * C + c + 4) = f32x4{v[4], v[5], v[6], v[7]};
     }
     if (planes) {
-        const u32x4 h = {T::pack2(v[0], v[1]), T::pack2(v[2], v[3]), T::pack2(v[4], v[5]), T::pack2(v[6], v[7])};
         *reinterpret_cast<u32x4*>(planes + row * C + c) = h;
-        if (NS == 2) {
-            u32x4 l;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const f32x2 u = T::unpack2(h[i]);
-                l[i] = T::pack2(v[2 * i] - u[0], v[2 * i + 1] - u[1]);
-            }
-            *reinterpret_cast<u32x4*>(planes + plane_stride + row * C + c) = l;
-        }
+        if (NS == 2) *reinterpret_cast<u32x4*>(planes + plane_stride + row * C + c) = l;
     }
 }
 
@@ -338,29 +332,36 @@ extern "C" size_t um_conv_stats_bytes(int batch, int parts, int channels) {
 
 static bool nhwc_channels_ok(int c) { return c > 0 && c % 8 == 0 && c <= 256; }
 
-extern "C" int um_nhwc_instance_norm(const float* x, const float* shortcut, const void* shortcut_planes, void* planes_out, float* f32_out, int batch,
-                                     int pixels, int channels, float eps, int normalize, int relu, const float* conv_stats, int conv_stats_parts,
-                                     void* workspace, size_t workspace_bytes, int mode, void* stream_) {
+static int nhwc_instance_norm_impl(const char* who, const float* x, const float* shortcut, const void* shortcut_planes, void* planes_out,
+                                   float* f32_out, int batch, int pixels, int channels, float eps, int normalize, int relu,
+                                   const float* conv_stats, int conv_stats_parts, const float* sc_conv_stats, int sc_conv_stats_parts,
+                                   void* workspace, size_t workspace_bytes, int mode, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!x || (!planes_out && !f32_out) || batch <= 0 || pixels <= 0 || !nhwc_channels_ok(channels) || (mode != 0 && mode != 1)) {
-        um_set_error("um_nhwc_instance_norm: bad argument (batch=%d pixels=%d channels=%d: channels must be a multiple of 8, <= 256)",
-                     batch, pixels, channels);
+        um_set_error("%s: bad argument (batch=%d pixels=%d channels=%d: channels must be a multiple of 8, <= 256)", who, batch, pixels,
+                     channels);
+        return -1;
+    }
+    if (sc_conv_stats && (!shortcut || !normalize || sc_conv_stats_parts <= 0)) {
+        um_set_error("%s: shortcut statistics go with an fp32 shortcut, normalize = 1 and sc_conv_stats_parts = um_conv_stats_parts() of "
+                     "the shortcut's convolution", who);
         return -1;
     }
     const long rows = (long)batch * pixels;
     const int nchunk = (pixels + NHWC_CHUNK_ROWS - 1) / NHWC_CHUNK_ROWS;
     float* partial = (float*)workspace;
-    float* stats = nullptr;
+    float *stats = nullptr, *sc_stats = nullptr;
     ScopedKernelTimer timer(UM_K_INSTANCE_NORM, stream);
     if (normalize) {
-        if (!workspace || workspace_bytes < um_nhwc_norm_workspace_bytes(batch, pixels, channels)) {
-            um_set_error("um_nhwc_instance_norm: workspace too small");
+        const size_t need = um_nhwc_norm_workspace_bytes(batch, pixels, channels) + (sc_conv_stats ? (size_t)batch * 2 * channels * sizeof(float) : 0);
+        if (!workspace || workspace_bytes < need) {
+            um_set_error("%s: workspace too small", who);
             return -3;
         }
         stats = partial + (long)batch * nchunk * 3 * channels;
         if (conv_stats) {                                          // per-tile statistics from the producing convolution
             if (conv_stats_parts <= 0) {
-                um_set_error("um_nhwc_instance_norm: conv_stats needs conv_stats_parts = um_conv_stats_parts() of the convolution");
+                um_set_error("%s: conv_stats needs conv_stats_parts = um_conv_stats_parts() of the convolution", who);
                 return -1;
             }
             hipLaunchKernelGGL(nhwc_stats_finalize_kernel, dim3(channels / 8, batch), dim3(256), 0, stream, conv_stats, stats, pixels, channels,
@@ -370,21 +371,54 @@ extern "C" int um_nhwc_instance_norm(const float* x, const float* shortcut, cons
             hipLaunchKernelGGL(nhwc_stats_finalize_kernel, dim3(channels / 8, batch), dim3(256), 0, stream, partial, stats, pixels, channels,
                                nchunk, NHWC_CHUNK_ROWS, eps);
         }
+        if (sc_conv_stats) {                                       // ... and the shortcut's, behind the first set
+            sc_stats = stats + (long)batch * 2 * channels;
+            hipLaunchKernelGGL(nhwc_stats_finalize_kernel, dim3(channels / 8, batch), dim3(256), 0, stream, sc_conv_stats, sc_stats, pixels,
+                               channels, sc_conv_stats_parts, 0, eps);
+        }
     }
     const long total = (rows + (planes_out ? 1 : 0)) * (channels / 8);
     const dim3 grid((unsigned)((total + 255) / 256));
     if (mode == 0)
-        hipLaunchKernelGGL((nhwc_apply_kernel<Fp16, 2>), grid, dim3(256), 0, stream, x, stats, shortcut,
+        hipLaunchKernelGGL((nhwc_apply_kernel<Fp16, 2>), grid, dim3(256), 0, stream, x, stats, shortcut, sc_stats,
                            (const unsigned short*)shortcut_planes, (unsigned short*)planes_out, f32_out, rows, pixels, channels, relu);
     else
-        hipLaunchKernelGGL((nhwc_apply_kernel<Bf16, 1>), grid, dim3(256), 0, stream, x, stats, shortcut,
+        hipLaunchKernelGGL((nhwc_apply_kernel<Bf16, 1>), grid, dim3(256), 0, stream, x, stats, shortcut, sc_stats,
                            (const unsigned short*)shortcut_planes, (unsigned short*)planes_out, f32_out, rows, pixels, channels, relu);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        um_set_error("um_nhwc_instance_norm: launch failed: %s", hipGetErrorString(e));
+        um_set_error("%s: launch failed: %s", who, hipGetErrorString(e));
         return (int)e;
     }
     return 0;
+}
+
+extern "C" int um_nhwc_instance_norm(const float* x, const float* shortcut, const void* shortcut_planes, void* planes_out, float* f32_out, int batch,
+                                     int pixels, int channels, float eps, int normalize, int relu, const float* conv_stats, int conv_stats_parts,
+                                     void* workspace, size_t workspace_bytes, int mode, void* stream_) {
+    return nhwc_instance_norm_impl("um_nhwc_instance_norm", x, shortcut, shortcut_planes, planes_out, f32_out, batch, pixels, channels, eps,
+                                   normalize, relu, conv_stats, conv_stats_parts, nullptr, 0, workspace, workspace_bytes, mode, stream_);
+}
+
+// um_nhwc_instance_norm whose fp32 shortcut is a projection's RAW output with the per-tile statistics its convolution left: the
+// shortcut's own InstanceNorm (no ReLU) is computed in registers -- the value a separate normalisation pass would have stored and
+// this one read back, bit for bit.  Workspace: um_nhwc_norm_sc_workspace_bytes().
+extern "C" size_t um_nhwc_norm_sc_workspace_bytes(int batch, int pixels, int channels) {
+    if (batch <= 0 || pixels <= 0 || channels <= 0) return 0;
+    return um_nhwc_norm_workspace_bytes(batch, pixels, channels) + (size_t)batch * 2 * channels * sizeof(float);
+}
+
+extern "C" int um_nhwc_instance_norm_sc(const float* x, const float* shortcut, const void* shortcut_planes, void* planes_out, float* f32_out,
+                                        int batch, int pixels, int channels, float eps, int normalize, int relu, const float* conv_stats,
+                                        int conv_stats_parts, void* workspace, size_t workspace_bytes, int mode, void* stream_,
+                                        const float* sc_conv_stats, int sc_conv_stats_parts) {
+    if (!sc_conv_stats) {
+        um_set_error("um_nhwc_instance_norm_sc: no shortcut statistics (um_nhwc_instance_norm is the entry without them)");
+        return -1;
+    }
+    return nhwc_instance_norm_impl("um_nhwc_instance_norm_sc", x, shortcut, shortcut_planes, planes_out, f32_out, batch, pixels, channels,
+                                   eps, normalize, relu, conv_stats, conv_stats_parts, sc_conv_stats, sc_conv_stats_parts, workspace,
+                                   workspace_bytes, mode, stream_);
 }
 
 extern "C" int um_nhwc_stats_finalize(const float* conv_stats, int conv_stats_parts, float* stats_out, int batch, int pixels, int channels,

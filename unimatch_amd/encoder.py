@@ -7,6 +7,8 @@ unimatch/trident_conv.py:10-90 so that reference checkpoints load unchanged
 (``backbone.conv1.weight``, ``backbone.layer2.0.downsample.0.bias``, ``backbone.trident_conv.weight`` ...).
 """
 
+import collections
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -14,6 +16,9 @@ import torch.nn.functional as F
 
 def _conv3(cin, cout, stride=1):
     return nn.Conv2d(cin, cout, 3, stride=stride, padding=1, bias=False)
+
+
+_Deferred = collections.namedtuple('_Deferred', 'u stats shortcut_planes')     # a block output whose normalisation the next block does
 
 
 class _Residual(nn.Module):
@@ -38,29 +43,59 @@ class _Residual(nn.Module):
         return F.relu((x if self.downsample is None else self.downsample(x)) + y)
 
 
-    def forward_nhwc(self, act, ops, want_f32):
+    def entry_fusable(self, ops, h, w, cin):
+        """True when this block's input can stay unwritten: a stride-2 block with a projection shortcut whose first convolution and
+        projection ``ops.conv2d_entry`` serves in one launch (``HipOps.fused_entry``)."""
+        return (getattr(ops, 'fused_entry', False) and self.downsample is not None and self.conv1.stride[0] == 2 and
+                ops.conv2d_entry_supported(h, w, cin, self.conv1.weight, self.downsample[0].weight))
+
+    def forward_nhwc(self, act, ops, want_f32, defer=False):
         """Channels-last path on the matrix cores: ``act = (planes, f32 | None, b, h, w, c)`` (operand planes of the block
         input).  Every normalisation kernel writes the next convolution's operand planes directly; the identity shortcut is
         read back from those planes (hi + lo), so no fp32 copy of a block's input exists; ``want_f32`` asks for an fp32 copy
-        of the output as well."""
+        of the output as well.
+
+        ``defer``: the next block is ``entry_fusable`` -- this block (identity shortcut held as planes) skips its output
+        normalisation and hands on ``_Deferred(u, statistics of u, shortcut planes)`` in place of the planes; the next block
+        builds its input from that while its convolutions stage it.  A block whose shortcut is an fp32 tensor
+        (``CNNEncoder.shortcut_f32``) ignores ``defer``: the entry kernel reads the shortcut as planes only, so this block
+        normalises as usual and the next one takes the plain convolutions (it checks what it was handed, not the flag)."""
         planes, f32, b, h, w, c = act
         stride = self.conv1.stride[0]
         cout = self.conv1.out_channels
-        t, ho, wo = ops.conv2d_nhwc((planes, b, h, w, c), self.conv1.weight, None, stride, (1, 1), stats=True)
+        fused = getattr(ops, 'fused_entry', False)
+        d = dstats = None
+        if isinstance(planes, _Deferred):
+            # conv1 and the projection in one launch; the block input relu(norm(u) + shortcut) is never written
+            proj = self.downsample[0]
+            t, d, ho, wo, tstats, dstats = ops.conv2d_entry(planes.u, planes.stats, planes.shortcut_planes, (b, h, w, c), self.conv1.weight,
+                                                            proj.weight, proj.bias)
+        else:
+            t, ho, wo = ops.conv2d_nhwc((planes, b, h, w, c), self.conv1.weight, None, stride, (1, 1), stats=True)
+            tstats = ops.last_conv_stats
         if getattr(ops, 'norm_on_load', False) and ops.conv2d_norm_supported(ho, wo, cout, self.conv2.weight):
             # the middle normalisation has one reader: conv2 normalises t while it stages its operand, no planes of t exist
-            u, _, _ = ops.conv2d_nhwc_normed(t, ops.last_conv_stats, (b, ho, wo, cout), self.conv2.weight, stats=True)
+            u, _, _ = ops.conv2d_nhwc_normed(t, tstats, (b, ho, wo, cout), self.conv2.weight, stats=True)
         else:
-            tp, _ = ops.nhwc_norm(t, b, ho * wo, relu=True, want_planes=True, conv_stats=ops.last_conv_stats)
+            tp, _ = ops.nhwc_norm(t, b, ho * wo, relu=True, want_planes=True, conv_stats=tstats)
             u, _, _ = ops.conv2d_nhwc((tp, b, ho, wo, cout), self.conv2.weight, None, 1, (1, 1), stats=True)
         ustats = ops.last_conv_stats
         sc = scp = None
         if self.downsample is None:
             sc, scp = (f32, None) if f32 is not None else (None, planes)
+            if defer and scp is not None:
+                return _Deferred(u, ustats, scp), None, b, ho, wo, cout
         else:
-            proj = self.downsample[0]
-            d, _, _ = ops.conv2d_nhwc((planes, b, h, w, c), proj.weight, proj.bias, stride, (0, 0), stats=True)
-            _, sc = ops.nhwc_norm(d, b, ho * wo, relu=False, want_planes=False, want_f32=True, conv_stats=ops.last_conv_stats)
+            if d is None:
+                proj = self.downsample[0]
+                d, _, _ = ops.conv2d_nhwc((planes, b, h, w, c), proj.weight, proj.bias, stride, (0, 0), stats=True)
+                dstats = ops.last_conv_stats
+            if fused:
+                # the projection's own normalisation has one reader, the output apply below: it normalises d while it loads it
+                op, of = ops.nhwc_norm(u, b, ho * wo, relu=True, shortcut=d, shortcut_stats=dstats, want_planes=True, want_f32=want_f32,
+                                       conv_stats=ustats)
+                return op, of, b, ho, wo, cout
+            _, sc = ops.nhwc_norm(d, b, ho * wo, relu=False, want_planes=False, want_f32=True, conv_stats=dstats)
         op, of = ops.nhwc_norm(u, b, ho * wo, relu=True, shortcut=sc, shortcut_planes=scp, want_planes=True, want_f32=want_f32,
                                conv_stats=ustats)
         return op, of, b, ho, wo, cout
@@ -134,6 +169,13 @@ class CNNEncoder(nn.Module):
 
     shortcut_f32 = False
 
+    @staticmethod
+    def _out_geometry(blk, act):
+        """``(h, w, c)`` of ``blk``'s output for the input record ``act``."""
+        _, _, _, h, w, _ = act
+        s = blk.conv1.stride[0]
+        return (h - 1) // s + 1, (w - 1) // s + 1, blk.conv1.out_channels
+
     def _forward_nhwc(self, x, ops, input_norm=None):
         """The whole encoder in channels-last layout on the library's convolution / normalisation kernels
         (``um_stem_conv_fwd``, ``um_conv2d_fwd``, ``um_nhwc_instance_norm``).  The returned maps are NCHW *views* of NHWC memory, so
@@ -147,7 +189,9 @@ class CNNEncoder(nn.Module):
         blocks = [blk for layer in (self.layer1, self.layer2, self.layer3) for blk in layer]
         for i, blk in enumerate(blocks):
             nxt = blocks[i + 1] if i + 1 < len(blocks) else None
-            act = blk.forward_nhwc(act, ops, want_f32=keep_f32 and nxt is not None and nxt.downsample is None)
+            # a stride-2 block builds its input from (u, statistics, shortcut planes) itself when its entry kernel serves the shape
+            defer = nxt is not None and blk.downsample is None and nxt.entry_fusable(ops, *self._out_geometry(blk, act))
+            act = blk.forward_nhwc(act, ops, want_f32=keep_f32 and nxt is not None and nxt.downsample is None, defer=defer)
         planes, _, b, h, w, c = act
         out, _, _ = ops.conv2d_nhwc((planes, b, h, w, c), self.conv2.weight, self.conv2.bias, 1, (0, 0))
         if self.num_branch == 1:

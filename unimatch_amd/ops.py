@@ -154,6 +154,8 @@ class HipOps(WorkspaceRegistry):
     # (class attributes: tests and tools/ab_bench.py flip them programmatically; the product reads no environment variable)
     fused_conv = True          # encoder convolutions + InstanceNorm in NHWC on um_conv2d_fwd / um_nhwc_instance_norm
     norm_on_load = True        # ... a residual block's middle InstanceNorm + ReLU inside its second convolution (um_conv2d_norm_fwd)
+    fused_entry = True         # ... a stride-2 block's input apply, first convolution and projection shortcut in one launch (um_conv2d_entry_fwd),
+                               #     and the projection's own InstanceNorm inside the block's output apply (um_nhwc_instance_norm_sc)
     CONV_MODE = 0              # ... always in the exact arithmetic: 'fast' (bf16) is a property of the matching path only
     WSHIFT = 10                # weights are scaled by 2^10 before the fp16 split (exact), see linear.hip
 
@@ -759,6 +761,47 @@ class HipOps(WorkspaceRegistry):
         _abi.check(code, 'um_conv2d_norm_fwd')
         return out, h, w
 
+    def conv2d_entry_supported(self, h, w, cin, weight, proj_weight, stride=2, padding=(1, 1)):
+        """True when ``conv2d_entry`` serves this transition block (``um_conv2d_entry_supported``: a pure function of the geometry)."""
+        cout, wcin, kh, kw = weight.shape
+        ph, pw = (padding, padding) if isinstance(padding, int) else padding
+        return (wcin == cin and tuple(proj_weight.shape) == (cout, cin, 1, 1) and
+                bool(self.lib.um_conv2d_entry_supported(h, w, cin, cout, kh, kw, stride, ph, pw, self.CONV_MODE)))
+
+    def conv2d_entry(self, u, conv_stats, shortcut_planes, geom, weight, proj_weight, proj_bias, eps=1e-5):
+        """A stride-2 residual block's entry in one launch (``um_conv2d_entry_fwd``): with ``X = relu(instance_norm(u) + shortcut)`` --
+        the block input, which is never written -- returns ``(t, d, ho, wo, t_stats, d_stats)``: ``t = conv3x3/2(X)`` with ``weight``,
+        ``d = conv1x1/2(X) + proj_bias`` and the ``last_conv_stats`` pair of each.  ``u`` is the fp32 NHWC output ``[b*h*w, cin]`` of the
+        previous block's second convolution, ``conv_stats`` the pair it left, ``shortcut_planes`` that block's shortcut as operand
+        planes.  Bit for bit ``nhwc_norm(u, shortcut_planes=)`` -> ``conv2d_nhwc`` twice."""
+        b, h, w, cin = geom
+        self._check_rows('u', u, cin)
+        if u.shape[0] != b * h * w:
+            raise ValueError('conv2d_entry: u must have b * h * w rows')
+        if shortcut_planes.numel() != self.lib.um_planes_bytes(b * h * w + 1, cin, self.CONV_MODE):
+            raise ValueError('conv2d_entry: shortcut_planes must be operand planes of [b * h * w + 1, cin]')
+        wp, cout, wcin, kh, kw = self.conv_weight_planes(weight)
+        wp2, cout2, wcin2, kh2, kw2 = self.conv_weight_planes(proj_weight)
+        if wcin != cin or (cout2, wcin2, kh2, kw2) != (cout, cin, 1, 1):
+            raise ValueError('conv2d_entry: the weights do not fit the activation / each other')
+        nstats = torch.empty((b, 2, cin), dtype=torch.float32, device=u.device)          # per call: one buffer per stream lane
+        _abi.check(self._launch('instance_norm', lambda: self.lib.um_nhwc_stats_finalize(
+            _ptr(conv_stats[0]), conv_stats[1], _ptr(nstats), b, h * w, cin, float(eps), _stream())), 'um_nhwc_stats_finalize')
+        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        t = torch.empty((b * ho * wo, cout), dtype=torch.float32, device=u.device)
+        d = torch.empty_like(t)
+        parts = self.lib.um_conv_stats_parts(h, w, cout, 3, 3, 2, 1, 1)
+        nst = self.lib.um_conv_stats_bytes(b, parts, cout) // 4
+        st_t = torch.empty(nst, dtype=torch.float32, device=u.device)
+        st_d = torch.empty(nst, dtype=torch.float32, device=u.device)
+        meta = {'flops': 2.0 * b * ho * wo * cout * 10 * cin}
+        code = self._launch('conv', lambda: self.lib.um_conv2d_entry_fwd(
+            _ptr(u), _ptr(nstats), _ptr(shortcut_planes), _ptr(wp), _ptr(wp2), _ptr(proj_bias) if proj_bias is not None else None, _ptr(t), _ptr(d), _ptr(st_t), _ptr(st_d),
+            b, h, w, cin, cout, 3, 3, 2, 1, 1, self.WSHIFT, self.CONV_MODE, _stream()), meta)
+        _abi.check(code, 'um_conv2d_entry_fwd')
+        self.last_conv_stats = (st_t, parts)
+        return t, d, ho, wo, (st_t, parts), (st_d, parts)
+
     def nhwc_planes_from(self, pieces, pad_to=32):
         """Operand planes of the channel concatenation of fp32 NHWC pieces ``[rows, c_i]`` (zero-padded to a multiple of
         ``pad_to`` channels): returns ``(planes, channels)``."""
@@ -980,10 +1023,12 @@ class HipOps(WorkspaceRegistry):
         return out, ho, wo
 
     def nhwc_norm(self, x, b, pixels, normalize=True, relu=True, shortcut=None, want_planes=True, want_f32=False, eps=1e-5,
-                  conv_stats=None, shortcut_planes=None):
+                  conv_stats=None, shortcut_planes=None, shortcut_stats=None):
         """InstanceNorm (+ ReLU, + shortcut + ReLU) of fp32 NHWC ``x [b*pixels, c]`` -> ``(planes | None, f32 | None)``.
         The shortcut is fp32 ``[b*pixels, c]`` or (``shortcut_planes``) operand planes of the same shape; ``conv_stats`` is the
-        ``(statistics, parts per image)`` pair the producing convolution left in ``last_conv_stats``."""
+        ``(statistics, parts per image)`` pair the producing convolution left in ``last_conv_stats``.  ``shortcut_stats``: such a
+        pair for an fp32 ``shortcut`` that is a projection's raw output -- its own InstanceNorm is applied on load
+        (``um_nhwc_instance_norm_sc``) instead of in a pass of its own."""
         self._check_rows('x', x, x.shape[1])
         c = x.shape[1]
         if x.shape[0] != b * pixels:
@@ -996,6 +1041,17 @@ class HipOps(WorkspaceRegistry):
         planes = (torch.empty(self.lib.um_planes_bytes(rows + 1, c, self.CONV_MODE), dtype=torch.uint8, device=x.device)
                   if want_planes else None)
         f32 = torch.empty_like(x) if want_f32 else None
+        if shortcut_stats is not None:
+            if shortcut is None or not normalize:
+                raise ValueError('nhwc_norm: shortcut_stats go with an fp32 shortcut and normalize=True')
+            ws = self._ws(self.lib.um_nhwc_norm_sc_workspace_bytes(b, pixels, c), x.device)
+            code = self._launch('instance_norm', lambda: self.lib.um_nhwc_instance_norm_sc(
+                _ptr(x), _ptr(shortcut), None, _ptr(planes) if planes is not None else None,
+                _ptr(f32) if f32 is not None else None, b, pixels, c, float(eps), 1, int(bool(relu)),
+                _ptr(conv_stats[0]) if conv_stats is not None else None, conv_stats[1] if conv_stats is not None else 0,
+                _ptr(ws), ws.numel(), self.CONV_MODE, _stream(), _ptr(shortcut_stats[0]), shortcut_stats[1]))
+            _abi.check(code, 'um_nhwc_instance_norm_sc')
+            return planes, f32
         ws = self._ws(self.lib.um_nhwc_norm_workspace_bytes(b, pixels, c), x.device) if normalize else None
         code = self._launch('instance_norm', lambda: self.lib.um_nhwc_instance_norm(
             _ptr(x), _ptr(shortcut) if shortcut is not None else None,
