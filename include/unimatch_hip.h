@@ -316,6 +316,14 @@ int um_conv2d_gru_add_fwd(int gate, const void* a_planes, int a_ld, int a_coff, 
                           const float* addend, int addend_ld, float* hidden, const float* z, int z_ld, float* z_out, int z_out_ld,
                           void* out_planes, int outp_ld, int outp_coff, long outp_rows, int batch, int hi, int wi, int cin,
                           int channels, int kh, int kw, int pad_h, int pad_w, int wshift, int mode, void* stream);
+/* um_conv2d_fwd (no activation, no statistics) with an fp32 addend in the epilogue: out = (acc * 2^-wshift + bias) + addend -- the value
+ * the plain launch stores, then ONE fp32 add of its own (nothing is contracted across the two), so the result is bit for bit
+ * um_conv2d_fwd's plus the addend.  addend: 16-byte aligned, addend_ld >= cout, a multiple of 4.  addend_period = 0: one row per output
+ * pixel, [batch*ho*wo][addend_ld]; addend_period = 1: ONE table [ho*wo][addend_ld] that serves every image (row = pixel inside the image):
+ * the Transformer's position table (unimatch/unimatch.py:139, feature_add_position) in the encoder's last convolution. */
+int um_conv2d_addend_fwd(const void* a_planes, const void* w_planes, const float* bias, const float* addend, int addend_ld,
+                         int addend_period, float* out, int batch, int hi, int wi, int cin, int cout, int kh, int kw, int stride,
+                         int pad_h, int pad_w, int wshift, int mode, void* stream);
 /* stats_out (optional): per output tile part (<= 128 pixels, in the order of the serving kernel's tiles) the (mean, pixel
  * count, sum of squared deviations) of every output channel, computed in the epilogue from the tile that is in LDS anyway.
  * um_conv_stats_parts() = parts per image for that geometry (the stem, um_conv7_fwd / um_stem_conv_fwd: kh = kw = 7,
@@ -344,6 +352,14 @@ int um_stem_conv_fwd(const float* image, int normalize, const float* mean3, cons
                      const void* w_planes, float* out, float* stats_out, int batch, int h, int w, int cout, int wshift,
                      void* stream);
 
+/* um_stem_conv_fwd of the batch [image0; image1] -- batch0 + batch1 images of one size in two tensors (the two images of every pair,
+ * unimatch/unimatch.py:126 concatenates them) -- without the concatenation: the packing kernel picks its source by image index.
+ * image_planes: um_stem_planes_bytes(batch0 + batch1, h, w).  Planes, launch, statistics and output are bit for bit those of
+ * um_stem_conv_fwd on the concatenated batch. */
+int um_stem_conv_pair_fwd(const float* image0, int batch0, const float* image1, int batch1, int normalize, const float* mean3,
+                          const float* std3, void* image_planes, const void* w_planes, float* out, float* stats_out, int h, int w,
+                          int cout, int wshift, void* stream);
+
 /* nn.InstanceNorm2d (affine=False, biased variance) + ReLU (+ shortcut add + ReLU) of unimatch/backbone.py:7-36 in NHWC:
  *   y = x (normalize == 0) | (x - mean_{b,c}) * rsqrt(var_{b,c} + eps);  y = relu(y) if relu;  y = relu(shortcut + y) if
  * shortcut.  x, shortcut: fp32 [batch*pixels][channels]; alternatively (shortcut == NULL) shortcut_planes: the shortcut as
@@ -355,6 +371,14 @@ size_t um_nhwc_norm_workspace_bytes(int batch, int pixels, int channels);
 int um_nhwc_instance_norm(const float* x, const float* shortcut, const void* shortcut_planes, void* planes_out, float* f32_out,
                           int batch, int pixels, int channels, float eps, int normalize, int relu, const float* conv_stats,
                           int conv_stats_parts, void* workspace, size_t workspace_bytes, int mode, void* stream);
+
+/* The channel concatenation [map | tokens | zero pad] as operand planes in one launch (the upsampler head's input cat(flow, feature),
+ * unimatch/unimatch.py:56-58).  map: fp32 NCHW [batch][map_channels][pixels], 1 <= map_channels <= 4; tokens: fp32
+ * [batch*pixels][channels] (16-byte aligned, channels a multiple of 4, <= 256).  planes_out: [NS][batch*pixels + 1][cp], cp =
+ * map_channels + channels rounded up to a multiple of 32: the map in columns 0 .. map_channels-1, the tokens behind it, zero columns
+ * up to cp and the zero row -- bit for bit what um_nhwc_instance_norm(normalize = 0) writes for the fp32 concatenation. */
+int um_nhwc_concat_planes(const float* map, const float* tokens, void* planes_out, int batch, int pixels, int map_channels, int channels,
+                          int mode, void* stream);
 
 /* um_nhwc_instance_norm whose fp32 `shortcut` is a projection shortcut's RAW convolution output: its own InstanceNorm (no ReLU,
  * unimatch/backbone.py:24-25) is computed in registers from sc_conv_stats / sc_conv_stats_parts (the per-tile statistics that

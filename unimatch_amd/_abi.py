@@ -46,6 +46,7 @@ SIGNATURES = {
                                 _c_size_t, _c_void_p]),
     'um_kv4_fwd': (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p]),
     'um_conv2d_fwd': (_c_int, [_c_void_p] * 5 + [_c_int] * 13 + [_c_void_p]),
+    'um_conv2d_addend_fwd': (_c_int, [_c_void_p] * 4 + [_c_int, _c_int, _c_void_p] + [_c_int] * 12 + [_c_void_p]),
     'um_conv2d_ex': (_c_int, [_c_void_p, _c_int, _c_int, ctypes.c_long, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p,
                               _c_int, _c_int, ctypes.c_long, _c_void_p] + [_c_int] * 13 + [_c_void_p]),
     'um_nhwc_gate': (_c_int, [_c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, ctypes.c_long, ctypes.c_long,
@@ -70,6 +71,8 @@ SIGNATURES = {
     'um_conv7_fwd': (_c_int, [_c_void_p, _c_int, _c_int] + [_c_void_p] * 6 + [_c_int, _c_int, _c_void_p, _c_int, _c_int, ctypes.c_long,
                               _c_void_p] + [_c_int] * 7 + [_c_void_p]),
     'um_stem_conv_fwd': (_c_int, [_c_void_p, _c_int] + [_c_void_p] * 6 + [_c_int] * 5 + [_c_void_p]),
+    'um_stem_conv_pair_fwd': (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_int] + [_c_void_p] * 6 + [_c_int] * 4 + [_c_void_p]),
+    'um_nhwc_concat_planes': (_c_int, [_c_void_p] * 3 + [_c_int] * 5 + [_c_void_p]),
     'um_nhwc_norm_workspace_bytes': (_c_size_t, [_c_int] * 3),
     'um_nhwc_instance_norm': (_c_int, [_c_void_p] * 5 + [_c_int] * 3 + [ctypes.c_float, _c_int, _c_int, _c_void_p, _c_int, _c_void_p,
                                        _c_size_t, _c_int, _c_void_p]),

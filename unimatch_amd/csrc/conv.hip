@@ -64,6 +64,7 @@ struct ConvArgs {
     // context features and initial hidden state, unimatch.py:315-331) is computed once and comes in here (round 4).
     const float* addend;
     int addend_ld;
+    int addend_period;            // 1: the addend is ONE table [Ho*Wo][addend_ld] that serves every image (row = pixel of the image)
     int B, Hi, Wi, Cin, Ho, Wo, Cout;
     int KH, KW, stride, pad_h, pad_w;
     int M;                        // B * Ho * Wo
@@ -96,7 +97,8 @@ struct IntC {
     static constexpr int value = V;
 };
 
-template <typename T, int NS, int NT, int NT0, int NTP, int WSTRIDE>   // WSTRIDE: bytes of a wave's private staging block
+template <typename T, int NS, int NT, int NT0, int NTP, int WSTRIDE, bool ADDEND>   // WSTRIDE: bytes of a wave's private staging block;
+                                                                                    // ADDEND = false: the caller never has an addend (its registers are not spent)
 __device__ __forceinline__ void conv_epilogue_pass(const ConvArgs& a, f32x16 (&acc)[NT], unsigned char* lds, unsigned char* scratch,
                                                    int bt, int rloc0, int nvalid, int part0, bool dense_parts, int n0, int tid,
                                                    int wave, int lane, int half) {
@@ -122,7 +124,10 @@ __device__ __forceinline__ void conv_epilogue_pass(const ConvArgs& a, f32x16 (&a
     const int gate = a.gate;
     float* hbase = gate ? a.gate_h + rowbase * a.gate_c : nullptr;
     const float* zbase = gate == 2 ? a.gate_z + rowbase * a.gate_zld : nullptr;
-    const float* abase = a.addend ? a.addend + rowbase * a.addend_ld : nullptr;
+    const float* abase = ADDEND && a.addend ? a.addend + rowbase * a.addend_ld : nullptr;
+    // periodic addend: back to the image's first row.  Applied at the loads: with the choice folded into `abase` itself hipcc 7.2 (clang 22)
+    // stops with "Illegal instruction detected" (a v_cmp on src_shared_base) in this function
+    const long aback = ADDEND && a.addend_period ? (long)bt * P * a.addend_ld : 0L;
     float* hobase = gate == 2 ? a.gate_hout + rowbase * a.gate_hout_ld : nullptr;
     f32x4 ad[NSIDE][BATCH], gz[NSIDE][BATCH], gh[NSIDE][BATCH];
     auto preload = [&](int b, int slot) {                         // both compile-time constants once the callers' loops are unrolled
@@ -133,7 +138,7 @@ __device__ __forceinline__ void conv_epilogue_pass(const ConvArgs& a, f32x16 (&a
             const int r = idx / CPR, c = idx - r * CPR;
             const int col = nb + 4 * c;
             if (r < nrows && col < a.Cout) {
-                if (abase) ad[slot][j] = *reinterpret_cast<const f32x4*>(abase + (unsigned)(r * a.addend_ld + col));
+                if (abase) ad[slot][j] = *reinterpret_cast<const f32x4*>(abase - aback + (unsigned)(r * a.addend_ld + col));
                 if (gate == 1 && col >= a.gate_c) gh[slot][j] = *reinterpret_cast<const f32x4*>(hbase + (unsigned)(r * a.gate_c + col - a.gate_c));
                 if (gate == 2) {
                     gz[slot][j] = *reinterpret_cast<const f32x4*>(zbase + (unsigned)(r * a.gate_zld + col));
@@ -169,7 +174,7 @@ __device__ __forceinline__ void conv_epilogue_pass(const ConvArgs& a, f32x16 (&a
         if (a.bias) to_lds(act_tag, IntC<1>{});
         else to_lds(act_tag, IntC<0>{});
     };
-    switch (a.addend ? 0 : a.act) {                               // with an addend the activation waits for it (store_rows)
+    switch (ADDEND && a.addend ? 0 : a.act) {                               // with an addend the activation waits for it (store_rows)
         case 0: to_lds_b(IntC<0>{}); break;
         case 1: to_lds_b(IntC<1>{}); break;
         case 2: to_lds_b(IntC<2>{}); break;
@@ -306,7 +311,7 @@ __device__ __forceinline__ void conv_epilogue_pass(const ConvArgs& a, f32x16 (&a
         }
     };
     auto store_rows_g = [&](auto gate_tag) {
-        if (a.addend) store_rows(gate_tag, IntC<1>{});
+        if (ADDEND && a.addend) store_rows(gate_tag, IntC<1>{});
         else store_rows(gate_tag, IntC<0>{});
     };
     if (a.gate == 0) store_rows_g(IntC<0>{});
@@ -315,15 +320,15 @@ __device__ __forceinline__ void conv_epilogue_pass(const ConvArgs& a, f32x16 (&a
 }
 
 // NTE = n-tiles per epilogue pass (NT: the whole tile at once).
-template <typename T, int NS, int NT, int NTE = NT>
+template <typename T, int NS, int NT, int NTE = NT, bool ADDEND = true>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[NT], unsigned char* lds, unsigned char* scratch,
                                               int bt, int rloc0, int nvalid, int part0, bool dense_parts, int n0, int tid, int wave,
                                               int lane, int half) {
     constexpr int NP = NTE < NT ? NTE : NT;
     constexpr int WSTRIDE = 32 * (32 * NP * 4);
-    conv_epilogue_pass<T, NS, NT, 0, NP, WSTRIDE>(a, acc, lds, scratch, bt, rloc0, nvalid, part0, dense_parts, n0, tid, wave, lane, half);
+    conv_epilogue_pass<T, NS, NT, 0, NP, WSTRIDE, ADDEND>(a, acc, lds, scratch, bt, rloc0, nvalid, part0, dense_parts, n0, tid, wave, lane, half);
     if constexpr (NTE < NT)          // the wave's staging block is private and DS operations of a wave execute in order
-        conv_epilogue_pass<T, NS, NT, NTE, NT - NTE, WSTRIDE>(a, acc, lds, scratch, bt, rloc0, nvalid, part0, dense_parts, n0, tid, wave,
+        conv_epilogue_pass<T, NS, NT, NTE, NT - NTE, WSTRIDE, ADDEND>(a, acc, lds, scratch, bt, rloc0, nvalid, part0, dense_parts, n0, tid, wave,
                                                               lane, half);
 }
 
@@ -613,7 +618,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const ConvEntryArgs
 
     {
         const int rloc0 = pl0 + 32 * wave;
-        conv_epilogue<T, NS, NT>(a, acc, lds, lds + RING, bt, rloc0, min(32, max(0, P - rloc0)), bt * ((P + 127) / 128) + pl0 / 128, false,
+        conv_epilogue<T, NS, NT, NT, !ENTRY>(a, acc, lds, lds + RING, bt, rloc0, min(32, max(0, P - rloc0)), bt * ((P + 127) / 128) + pl0 / 128, false,
                                  n0, tid, wave, lane, half);
         if constexpr (ENTRY) {
             ConvArgs a2 = a;
@@ -621,7 +626,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const ConvEntryArgs
             a2.out = e.out2;
             a2.stats = e.stats2;
             __syncthreads();                     // the first epilogue's statistics scratch has been read
-            conv_epilogue<T, NS, NT>(a2, acc2, lds, lds + RING, bt, rloc0, min(32, max(0, P - rloc0)), bt * ((P + 127) / 128) + pl0 / 128,
+            conv_epilogue<T, NS, NT, NT, false>(a2, acc2, lds, lds + RING, bt, rloc0, min(32, max(0, P - rloc0)), bt * ((P + 127) / 128) + pl0 / 128,
                                      false, n0, tid, wave, lane, half);
         }
     }
@@ -1264,7 +1269,8 @@ static int conv2d_impl(const void* a_planes, int a_ld, int a_coff, long a_rows, 
                        float* stats_out, int batch, int hi, int wi, int cin, int cout, int kh, int kw, int stride,
                        int pad_h, int pad_w, int act, int wshift, int mode, void* stream_, int gate, float* gate_h,
                        const float* gate_z, int gate_zld, const float* addend = nullptr, int addend_ld = 0, float* gate_hout = nullptr,
-                       int gate_hout_ld = 0, const float* norm_x = nullptr, const float* norm_stats = nullptr, int norm_relu = 0) {
+                       int gate_hout_ld = 0, const float* norm_x = nullptr, const float* norm_stats = nullptr, int norm_relu = 0,
+                       int addend_period = 0) {
     const bool norm = norm_x != nullptr;                          // um_conv2d_norm_fwd: fp32 input + statistics instead of a_planes
     if (gate_hout && (gate != 2 || gate_hout_ld < cout || gate_hout_ld % 4 != 0 || ((unsigned long)gate_hout & 15) != 0)) {
         um_set_error("um_conv2d: a separate new-state tensor goes with gate 2 only: 16-byte aligned fp32 [M][ld >= channels, ld %% 4 == 0]");
@@ -1342,6 +1348,7 @@ static int conv2d_impl(const void* a_planes, int a_ld, int a_coff, long a_rows, 
     a.stats = stats_out;
     a.addend = addend;
     a.addend_ld = addend_ld;
+    a.addend_period = addend_period;
     a.B = batch;
     a.Hi = hi;
     a.Wi = wi;
@@ -1443,6 +1450,23 @@ extern "C" int um_conv2d_fwd(const void* a_planes, const void* w_planes, const f
                         cin, cout, kh, kw, stride, pad_h, pad_w, relu ? 1 : 0, wshift, mode, stream_);
 }
 
+// um_conv2d_fwd (no activation, no statistics) with a per-pixel addend in the epilogue: out = (acc * 2^-wshift + bias) + addend, the stored
+// value of the plain launch and then one fp32 add of its own (the sum goes through LDS in between: nothing contracts across the two).
+// addend_period = 0: fp32 [batch*ho*wo][addend_ld]; 1: ONE table [ho*wo][addend_ld] for every image -- the Transformer's position
+// table in the encoder's last convolution.
+extern "C" int um_conv2d_addend_fwd(const void* a_planes, const void* w_planes, const float* bias, const float* addend, int addend_ld,
+                                    int addend_period, float* out, int batch, int hi, int wi, int cin, int cout, int kh, int kw, int stride,
+                                    int pad_h, int pad_w, int wshift, int mode, void* stream_) {
+    if (!addend || !out || (addend_period != 0 && addend_period != 1)) {
+        um_set_error("um_conv2d_addend_fwd: needs an addend, an fp32 output and addend_period 0 | 1");
+        return -1;
+    }
+    const long rows_in = (long)batch * hi * wi;
+    return conv2d_impl(a_planes, cin, 0, rows_in + 1, w_planes, bias, out, cout, 0, nullptr, 0, 0, 0, nullptr, batch, hi, wi, cin, cout, kh,
+                       kw, stride, pad_h, pad_w, 0, wshift, mode, stream_, 0, nullptr, nullptr, 0, addend, addend_ld, nullptr, 0, nullptr,
+                       nullptr, 0, addend_period);
+}
+
 // um_conv2d_fwd whose input is the producing convolution's fp32 NHWC output x [batch*hi*wi][cin] and its finalized InstanceNorm
 // statistics [batch][2][cin] (um_nhwc_stats_finalize): relu?((x - mean) * rstd) is computed while the operand is staged
 // (conv_patch_norm_kernel), bit-identical to um_nhwc_instance_norm(planes) -> um_conv2d_fwd without that pass over memory.
@@ -1536,7 +1560,7 @@ extern "C" int um_conv2d_entry_fwd(const float* u, const float* ustats, const vo
 // pixel and the missing channels meet zero weights.  So the layer is a "7 x 1 convolution with 8 CPP input channels" whose
 // rows advance by one packed pixel: no im2col, no border logic, 16-byte aligned LDS-DMA (K = 224 / 448 instead of 49 C).
 template <int CPP>
-__global__ __launch_bounds__(256) void pack7_kernel(const float* img, unsigned short* planes, long plane_stride, int B, int C,
+__global__ __launch_bounds__(256) void pack7_kernel(const float* img, const float* img1, int B0, unsigned short* planes, long plane_stride, int B, int C,
                                                     int H, int W, int Hp, int Wp, int normalize, float m0, float m1, float m2,
                                                     float s0, float s1, float s2) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -1551,10 +1575,13 @@ __global__ __launch_bounds__(256) void pack7_kernel(const float* img, unsigned s
     for (int c = 0; c < CPP; ++c) v[c] = 0.f;
     if ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) {
         const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
+        // images 0 .. B0-1 come from img, the others from img1 (the two halves of a pair batch, never concatenated)
+        const float* src = b < B0 ? img : img1;
+        const int bl = b < B0 ? b : b - B0;
 #pragma unroll
         for (int c = 0; c < CPP; ++c) {
             if (c < C) {
-                float p = img[(((long)b * C + c) * H + y) * W + x];
+                float p = src[(((long)bl * C + c) * H + y) * W + x];
                 if (normalize && c < 3) p = (p / 255.0f - mean[c]) / sd[c];    // the reference's operation order (unimatch.py:122-124)
                 v[c] = p;
             }
@@ -1578,13 +1605,14 @@ extern "C" size_t um_conv7_planes_bytes(int batch, int h, int w, int stride) {
     return (size_t)(2 * ((long)batch * (h + 6) * conv7_wp(w) + 8) * cpp * 2);    // two fp16 planes, 8 pixels of slack
 }
 
-extern "C" int um_conv7_fwd(const float* image, int channels, int normalize, const float* mean3, const float* std3,
-                            void* image_planes, const void* w_planes, const float* bias, float* out, int out_ld, int out_coff,
-                            void* out_planes, int outp_ld, int outp_coff, long outp_rows, float* stats_out, int batch, int h,
-                            int w, int cout, int stride, int act, int wshift, void* stream_) {
+// image: images 0 .. batch0-1; image1 (batch0 < batch): the remaining ones, same [channels, h, w]
+static int conv7_impl(const float* image, const float* image1, int batch0, int channels, int normalize, const float* mean3, const float* std3,
+                      void* image_planes, const void* w_planes, const float* bias, float* out, int out_ld, int out_coff,
+                      void* out_planes, int outp_ld, int outp_coff, long outp_rows, float* stats_out, int batch, int h,
+                      int w, int cout, int stride, int act, int wshift, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const int cpp = stride == 2 ? 4 : 8;
-    if (!image || !image_planes || !w_planes || (!out && !out_planes) || batch <= 0 || h < 7 || w < 7 || cout <= 0 || cout % 4 != 0 ||
+    if (!image || batch0 <= 0 || batch0 > batch || (batch0 < batch && !image1) || !image_planes || !w_planes || (!out && !out_planes) || batch <= 0 || h < 7 || w < 7 || cout <= 0 || cout % 4 != 0 ||
         wshift < 0 || wshift > 14 || (stride != 1 && stride != 2) || channels <= 0 || channels > (stride == 2 ? 3 : 8) ||
         (normalize && (!mean3 || !std3)) || act < 0 || act > 3) {
         um_set_error("um_conv7_fwd: bad argument (batch=%d channels=%d h=%d w=%d cout=%d stride=%d)", batch, channels, h, w, cout, stride);
@@ -1617,10 +1645,10 @@ extern "C" int um_conv7_fwd(const float* image, int channels, int normalize, con
         const float ss[3] = {normalize ? std3[0] : 1.f, normalize ? std3[1] : 1.f, normalize ? std3[2] : 1.f};
         const dim3 grid((unsigned)((rows + 255) / 256));
         if (cpp == 4)
-            hipLaunchKernelGGL((pack7_kernel<4>), grid, dim3(256), 0, stream, image, (unsigned short*)image_planes, plane_stride,
+            hipLaunchKernelGGL((pack7_kernel<4>), grid, dim3(256), 0, stream, image, image1, batch0, (unsigned short*)image_planes, plane_stride,
                                batch, channels, h, w, hp, wp, normalize, mm[0], mm[1], mm[2], ss[0], ss[1], ss[2]);
         else
-            hipLaunchKernelGGL((pack7_kernel<8>), grid, dim3(256), 0, stream, image, (unsigned short*)image_planes, plane_stride,
+            hipLaunchKernelGGL((pack7_kernel<8>), grid, dim3(256), 0, stream, image, image1, batch0, (unsigned short*)image_planes, plane_stride,
                                batch, channels, h, w, hp, wp, normalize, mm[0], mm[1], mm[2], ss[0], ss[1], ss[2]);
     }
     ConvArgs a;
@@ -1641,6 +1669,7 @@ extern "C" int um_conv7_fwd(const float* image, int channels, int normalize, con
     a.stats = stats_out;
     a.addend = nullptr;
     a.addend_ld = 0;
+    a.addend_period = 0;
     a.B = batch;
     a.Hi = hp;
     a.Wi = wp;
@@ -1674,6 +1703,14 @@ extern "C" int um_conv7_fwd(const float* image, int channels, int normalize, con
     return 0;
 }
 
+extern "C" int um_conv7_fwd(const float* image, int channels, int normalize, const float* mean3, const float* std3,
+                            void* image_planes, const void* w_planes, const float* bias, float* out, int out_ld, int out_coff,
+                            void* out_planes, int outp_ld, int outp_coff, long outp_rows, float* stats_out, int batch, int h,
+                            int w, int cout, int stride, int act, int wshift, void* stream_) {
+    return conv7_impl(image, nullptr, batch, channels, normalize, mean3, std3, image_planes, w_planes, bias, out, out_ld, out_coff, out_planes,
+                      outp_ld, outp_coff, outp_rows, stats_out, batch, h, w, cout, stride, act, wshift, stream_);
+}
+
 extern "C" size_t um_stem_planes_bytes(int batch, int h, int w) { return um_conv7_planes_bytes(batch, h, w, 2); }
 
 extern "C" int um_stem_conv_fwd(const float* image, int normalize, const float* mean3, const float* std3, void* image_planes,
@@ -1681,4 +1718,18 @@ extern "C" int um_stem_conv_fwd(const float* image, int normalize, const float* 
                                 int wshift, void* stream_) {
     return um_conv7_fwd(image, 3, normalize, mean3, std3, image_planes, w_planes, nullptr, out, cout, 0, nullptr, 0, 0, 0, stats_out,
                         batch, h, w, cout, 2, 0, wshift, stream_);
+}
+
+// um_stem_conv_fwd of the batch [image0; image1] (batch0 + batch1 images of one size) without the concatenation: the packing kernel
+// reads every input pixel exactly once anyway and picks its source by image index.  Planes, launch, statistics and output are those
+// of um_stem_conv_fwd on the concatenated batch.
+extern "C" int um_stem_conv_pair_fwd(const float* image0, int batch0, const float* image1, int batch1, int normalize, const float* mean3,
+                                     const float* std3, void* image_planes, const void* w_planes, float* out, float* stats_out, int h, int w,
+                                     int cout, int wshift, void* stream_) {
+    if (!image0 || !image1 || batch0 <= 0 || batch1 <= 0) {
+        um_set_error("um_stem_conv_pair_fwd: two image tensors with a positive batch each (batch0=%d batch1=%d)", batch0, batch1);
+        return -1;
+    }
+    return conv7_impl(image0, image1, batch0, 3, normalize, mean3, std3, image_planes, w_planes, nullptr, out, cout, 0, nullptr, 0, 0, 0,
+                      stats_out, batch0 + batch1, h, w, cout, 2, 0, wshift, stream_);
 }

@@ -271,6 +271,49 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* x, unsig
     }
 }
 
+// ---- channel concatenation [map | tokens | zero pad] straight into operand planes (the upsampler head's input, unimatch.py:56-58:
+// cat(flow, feature)).  map: fp32 NCHW [B][V][P] (V <= 4), tokens: fp32 [B*P][C]; planes [NS][rows + 1][CP], CP = V + C rounded up to 32:
+// columns 0 .. V-1 the map, V .. V+C-1 the tokens, zeros behind, and the zero row.  A workgroup takes R = 256 / (CP / 8) rows: their
+// token rows are one contiguous block, loaded with aligned 16-byte loads into LDS (the V-column prefix shifts every token row by 4 V
+// bytes against the 16-byte stores); one thread = 8 output columns of one row, split by um_norm_value8 (no norm, no ReLU): the bits
+// nhwc_apply_kernel writes for the same fp32 values.
+template <typename T, int NS>
+__global__ __launch_bounds__(256) void nhwc_concat_planes_kernel(const float* map, const float* tokens, unsigned short* planes, long rows,
+                                                                 int P, int V, int C, int CP) {
+    __shared__ float tile[2048];                                  // R * C <= 256 * 8 * C / CP < 2048
+    const int tpr = CP >> 3, R = 256 / tpr;
+    const long r0 = (long)blockIdx.x * R;
+    const long left = rows - r0;
+    const int nr = (int)(left < R ? (left > 0 ? left : 0) : R);   // token rows of this workgroup (the zero row has none)
+    const f32x4* src = reinterpret_cast<const f32x4*>(tokens + r0 * C);
+    for (int i = threadIdx.x; i < nr * (C >> 2); i += 256) reinterpret_cast<f32x4*>(tile)[i] = src[i];
+    __syncthreads();
+    const int lr = threadIdx.x / tpr, j = threadIdx.x - lr * tpr;
+    const long row = r0 + lr;
+    if (lr >= R || row > rows) return;
+    const long plane_stride = (rows + 1) * CP;
+    unsigned short* dst = planes + row * CP + 8 * j;
+    if (row == rows) {
+        const u32x4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int pl = 0; pl < NS; ++pl) *reinterpret_cast<u32x4*>(dst + pl * plane_stride) = z;
+        return;
+    }
+    const long b = row / P, p = row - b * P;
+    float v[8], zf[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int cc = 8 * j + i;
+        zf[i] = 0.f;
+        v[i] = cc < V ? map[(b * V + cc) * P + p] : cc < V + C ? tile[lr * C + cc - V] : 0.f;
+    }
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    u32x4 h, l;
+    um_norm_value8<T, NS>(v, false, zf, zf, false, 0, zf, false, zf, zf, z, z, true, h, l);
+    *reinterpret_cast<u32x4*>(dst) = h;
+    if (NS == 2) *reinterpret_cast<u32x4*>(dst + plane_stride) = l;
+}
+
 // ---- small channels-last helpers of the refinement block (SepConvGRU gate arithmetic, reg_refine.py:55-76) ------------------
 // One thread = 4 channels of one pixel.  mode 0: planes[coff + c] = src[c]                      (column scatter)
 //                                         mode 1: planes[coff + c] = zr[C + c] * h[c]             (r * h)
@@ -483,6 +526,35 @@ extern "C" int um_nhwc_gate(int mode, const float* src, int src_ld, const float*
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         um_set_error("um_nhwc_gate: launch failed: %s", hipGetErrorString(e));
+        return (int)e;
+    }
+    return 0;
+}
+
+extern "C" int um_nhwc_concat_planes(const float* map, const float* tokens, void* planes_out, int batch, int pixels, int map_channels,
+                                     int channels, int mode, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!map || !tokens || !planes_out || batch <= 0 || pixels <= 0 || map_channels < 1 || map_channels > 4 || channels <= 0 ||
+        channels % 4 != 0 || channels > 256 || ((unsigned long)tokens & 15) != 0 || ((unsigned long)planes_out & 15) != 0 ||
+        (mode != 0 && mode != 1)) {
+        um_set_error("um_nhwc_concat_planes: bad argument (batch=%d pixels=%d map_channels=%d channels=%d: 1..4 map channels, token "
+                     "channels a multiple of 4, <= 256, 16-byte aligned tokens / planes)", batch, pixels, map_channels, channels);
+        return -1;
+    }
+    const long rows = (long)batch * pixels;
+    const int cp = (map_channels + channels + 31) / 32 * 32;
+    const int r = 256 / (cp / 8);
+    const dim3 grid((unsigned)((rows + 1 + r - 1) / r));
+    ScopedKernelTimer timer(UM_K_INSTANCE_NORM, stream);
+    if (mode == 0)
+        hipLaunchKernelGGL((nhwc_concat_planes_kernel<Fp16, 2>), grid, dim3(256), 0, stream, map, tokens, (unsigned short*)planes_out, rows,
+                           pixels, map_channels, channels, cp);
+    else
+        hipLaunchKernelGGL((nhwc_concat_planes_kernel<Bf16, 1>), grid, dim3(256), 0, stream, map, tokens, (unsigned short*)planes_out, rows,
+                           pixels, map_channels, channels, cp);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        um_set_error("um_nhwc_concat_planes: launch failed: %s", hipGetErrorString(e));
         return (int)e;
     }
     return 0;

@@ -148,13 +148,22 @@ class CNNEncoder(nn.Module):
         """True when the channels-last path will run: it folds the input normalisation into the stem's image packing."""
         return ops is not None and getattr(ops, 'fused_conv', False) and x.is_cuda
 
-    def forward(self, x, ops=None, input_norm=None):
+    def forward(self, x, ops=None, input_norm=None, out_addend=None):
         """``ops``: a backend offering ``instance_norm`` (HipOps) fuses the normalisation / activation tail of
         every convolution; ``None`` keeps the stock PyTorch modules (CPU tests).  ``input_norm = (mean3, std3)``: the
-        images are raw 0..255 and still need ``(x / 255 - mean) / std`` (only passed when ``takes_raw_images``)."""
-        if self.takes_raw_images(ops, x):
-            return self._forward_nhwc(x, ops, input_norm)
-        assert input_norm is None
+        images are raw 0..255 and still need ``(x / 255 - mean) / std`` (only passed when ``takes_raw_images``).
+        ``x`` may be a tuple of image tensors: the encoder of their concatenation along the batch (two tensors of one size reach the
+        channels-last stem as they are, ``HipOps.fused_glue``).  ``out_addend(h, w)`` (channels-last path, one output scale) returns an
+        fp32 table ``[h*w, C]`` that the last convolution adds to every image's features in its epilogue."""
+        if isinstance(x, (tuple, list)):
+            x = tuple(x)
+            pair = (len(x) == 2 and self.takes_raw_images(ops, x[0]) and getattr(ops, 'fused_glue', False)
+                    and x[0].shape[1:] == x[1].shape[1:] and x[0].dtype == x[1].dtype == torch.float32 and x[0].device == x[1].device)
+            if not pair:
+                x = x[0] if len(x) == 1 else torch.cat(x, 0)
+        if self.takes_raw_images(ops, x[0] if isinstance(x, tuple) else x):
+            return self._forward_nhwc(x, ops, input_norm, out_addend)
+        assert input_norm is None and out_addend is None
         if ops is not None and getattr(ops, 'fused_tail', False) and x.is_cuda:
             x = ops.instance_norm(self.conv1(x), relu=True)
             for layer in (self.layer1, self.layer2, self.layer3):
@@ -176,12 +185,17 @@ class CNNEncoder(nn.Module):
         s = blk.conv1.stride[0]
         return (h - 1) // s + 1, (w - 1) // s + 1, blk.conv1.out_channels
 
-    def _forward_nhwc(self, x, ops, input_norm=None):
+    def _forward_nhwc(self, x, ops, input_norm=None, out_addend=None):
         """The whole encoder in channels-last layout on the library's convolution / normalisation kernels
         (``um_stem_conv_fwd``, ``um_conv2d_fwd``, ``um_nhwc_instance_norm``).  The returned maps are NCHW *views* of NHWC memory, so
         ``flatten(2).transpose(1, 2)`` downstream (token-major features) is free."""
-        b = x.shape[0]
-        y, h, w = ops.stem_conv(x.contiguous(), self.conv1.weight, input_norm, stats=True)    # fp32 NHWC [b*h*w, 64]
+        if isinstance(x, tuple):                                # the two halves of a pair batch, read where they are
+            b = x[0].shape[0] + x[1].shape[0]
+            x = tuple(t.contiguous() for t in x)
+        else:
+            b = x.shape[0]
+            x = x.contiguous()
+        y, h, w = ops.stem_conv(x, self.conv1.weight, input_norm, stats=True)    # fp32 NHWC [b*h*w, 64]
         c = y.shape[1]
         keep_f32 = self.shortcut_f32                            # A/B knob (tools/ab_bench.py --set): fp32 copies for the shortcuts
         planes, f32 = ops.nhwc_norm(y, b, h * w, relu=True, want_planes=True, want_f32=keep_f32, conv_stats=ops.last_conv_stats)
@@ -193,7 +207,11 @@ class CNNEncoder(nn.Module):
             defer = nxt is not None and blk.downsample is None and nxt.entry_fusable(ops, *self._out_geometry(blk, act))
             act = blk.forward_nhwc(act, ops, want_f32=keep_f32 and nxt is not None and nxt.downsample is None, defer=defer)
         planes, _, b, h, w, c = act
-        out, _, _ = ops.conv2d_nhwc((planes, b, h, w, c), self.conv2.weight, self.conv2.bias, 1, (0, 0))
+        if out_addend is not None:
+            assert self.num_branch == 1, 'the trident branches read the position-free features'
+            out, _, _ = ops.conv2d_nhwc((planes, b, h, w, c), self.conv2.weight, self.conv2.bias, 1, (0, 0), image_addend=out_addend(h, w))
+        else:
+            out, _, _ = ops.conv2d_nhwc((planes, b, h, w, c), self.conv2.weight, self.conv2.bias, 1, (0, 0))
         if self.num_branch == 1:
             return [out.view(b, h, w, -1).permute(0, 3, 1, 2)]
         tp, _ = ops.nhwc_norm(out, b, h * w, normalize=False, relu=False, want_planes=True)

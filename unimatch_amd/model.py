@@ -439,8 +439,16 @@ class UniMatch(nn.Module):
             b, v, h, w = flow2.shape
             rows = b * h * w
             feat = f0_map.permute(0, 2, 3, 1).reshape(rows, -1)          # a view when f0_map came from tokens
-            planes, cin = ops.nhwc_planes_from([flow2.permute(0, 2, 3, 1).reshape(rows, v), feat])
             c1, c2 = self.upsampler[0], self.upsampler[2]
+            if getattr(ops, 'fused_glue', False) and v <= 4:
+                # one launch builds the input planes; the hidden map leaves the 3x3's epilogue as the 1x1's operand planes
+                planes, cin = ops.nhwc_concat_planes(flow2.contiguous(), feat.contiguous())
+                hid = ops.cached_planes_buffer('upsampler_hidden', rows, c1.out_channels, flow2.device)
+                ops.conv_ex((planes, cin, 0, cin), (b, h, w), (ops.conv_weight_planes(ops.conv_weight_padded(c1.weight, cin)), c1.bias),
+                            (3, 3), 1, (1, 1), 1, outp=(hid, c1.out_channels, 0))
+                mask, _, _ = ops.conv2d_nhwc((hid, b, h, w, c1.out_channels), c2.weight, c2.bias, 1, (0, 0))
+                return mask, True
+            planes, cin = ops.nhwc_planes_from([flow2.permute(0, 2, 3, 1).reshape(rows, v), feat])
             hid, _, _ = ops.conv2d_nhwc((planes, b, h, w, cin), ops.conv_weight_padded(c1.weight, cin), c1.bias, 1, (1, 1),
                                         relu=True)
             hp, hc = ops.nhwc_planes_from([hid])
@@ -448,10 +456,11 @@ class UniMatch(nn.Module):
             return mask, True
         return self.upsampler(torch.cat([flow2, f0_map], 1)), False
 
-    def _upsample(self, flow2, f0_map, is_depth=False):
+    def _upsample(self, flow2, f0_map, is_depth=False, out=None):
+        """``out``: where the channels-last path writes the prediction (``HipOps.convex_upsample``); other paths ignore it."""
         mask, nhwc = self._upsample_mask(flow2, f0_map)
         if nhwc:
-            return self.ops.convex_upsample(flow2, mask, self.upsample_factor, is_depth, mask_nhwc=True)
+            return self.ops.convex_upsample(flow2, mask, self.upsample_factor, is_depth, mask_nhwc=True, out=out)
         return self._convex(flow2, mask, is_depth=is_depth)
 
     # ------------------------------------------------------------------ forward
@@ -529,12 +538,16 @@ class UniMatch(nn.Module):
             pk = dict(kw, intrinsics=shard_batch(intrinsics, r, parts), pose=shard_batch(pose, r, parts))
             return shard_batch(img0, r, parts), shard_batch(img1, r, parts), pk
 
-        def compute(r, ins):
+        def compute(r, ins, out=None):
             a0, a1, pk = ins
-            return self._forward_one(a0, a1, **pk)['flow_preds']
+            return self._forward_one(a0, a1, pred_out=out, **pk)['flow_preds']
 
         bidir = 2 if (pred_bidir_flow or pred_bidir_depth) else 1
-        return self._runner.run_parts(self, parts, batch, bidir, img0.shape, img0.device, kw, prepare, compute)
+        # a flow prediction is written by the parts' last launches straight into one tensor: no concatenation at the join
+        out_shape = None
+        if task == 'flow' and bidir == 1 and img0.is_cuda and getattr(self.ops, 'fused_glue', False):
+            out_shape = (batch, 2) + tuple(img0.shape[-2:])
+        return self._runner.run_parts(self, parts, batch, bidir, img0.shape, img0.device, kw, prepare, compute, out_shape=out_shape)
 
     def _plan_parts(self, parts, task, attn_type, batch, height, width, is_cuda):
         """How many concurrent parts a call of ``batch`` samples runs as: ``parts`` when given (``launch_parts``), else
@@ -680,8 +693,9 @@ class UniMatch(nn.Module):
     def _forward_one(self, img0, img1, attn_type=None, attn_splits_list=None, corr_radius_list=None,
                      prop_radius_list=None, num_reg_refine=1, pred_bidir_flow=False, task='flow', intrinsics=None,
                      pose=None, min_depth=1. / 0.5, max_depth=1. / 10, num_depth_candidates=64,
-                     depth_from_argmax=False, pred_bidir_depth=False):
-        """One forward of the given samples on the current stream."""
+                     depth_from_argmax=False, pred_bidir_depth=False, pred_out=None):
+        """One forward of the given samples on the current stream.  ``pred_out``: a contiguous ``[B, 2, H, W]`` tensor the flow
+        prediction may be written to (it is then the returned prediction; a path that cannot do so ignores it)."""
         if pred_bidir_flow:
             assert task == 'flow'
         if task == 'depth':
@@ -709,17 +723,24 @@ class UniMatch(nn.Module):
         if img1.device != dev:
             raise ValueError(f'img0 is on {dev} and img1 on {img1.device}')
         with guard, torch.no_grad():
-            feats = self._encode((img0, img1), task)
-            return self._match(feats, img0.shape[0], attn_type=attn_type, attn_splits_list=attn_splits_list,
+            # the position table goes into the encoder's last convolution where the encoder's output has one reader, the
+            # `stream=both + pos` branch of _match: one scale (no warp, no bidirectional stacking), no refinement (its ori0 / ori1 are
+            # position-free), no taps
+            with_pos = (self.num_scales == 1 and not self.reg_refine and self.debug_taps is None and getattr(ops, 'fused_glue', False)
+                        and self.backbone.takes_raw_images(ops, img0) and img0.shape == img1.shape)
+            pos = (lambda h, w: self._position(h, w, attn_splits_list[0], dev)) if with_pos else None
+            feats = self._encode((img0, img1), task, pos)
+            return self._match(feats, img0.shape[0], stream_has_pos=with_pos, pred_out=pred_out, attn_type=attn_type, attn_splits_list=attn_splits_list,
                                corr_radius_list=corr_radius_list, prop_radius_list=prop_radius_list, num_reg_refine=num_reg_refine,
                                pred_bidir_flow=pred_bidir_flow, task=task, intrinsics=intrinsics, pose=pose, min_depth=min_depth,
                                max_depth=max_depth, num_depth_candidates=num_depth_candidates, depth_from_argmax=depth_from_argmax,
                                pred_bidir_depth=pred_bidir_depth)
 
-    def _encode(self, images, task='flow'):
+    def _encode(self, images, task='flow', position=None):
         """The encode step: the CNN encoder of the images of the tuple ``images``, stacked in that order -> per-scale feature maps
         ``[N, C, h, w]``, low -> high resolution.  Strictly per image (InstanceNorm is per sample): a frame's features are the same
-        whichever pair asks for them."""
+        whichever pair asks for them.  ``position(h, w)``: the Transformer's position table, added by the encoder's last launch --
+        only for a caller whose one reader of the features wants them with it (``_forward_one``)."""
         ops = self.ops
         input_norm = None
         if task == 'flow':                  # stereo / depth loaders normalise already (unimatch.py:122-124)
@@ -728,14 +749,22 @@ class UniMatch(nn.Module):
             else:
                 mean, std = self._constants(images[0].device)
                 images = tuple((im / 255. - mean) / std for im in images)
-        stack = images[0] if len(images) == 1 else torch.cat(images, 0)
+        # two tensors of one size reach the channels-last stem as they are (it reads every pixel once anyway); every other case -- one
+        # tensor, three or more (video), the CPU and the NCHW paths -- is stacked here
+        pair = (len(images) == 2 and getattr(ops, 'fused_glue', False) and self.backbone.takes_raw_images(ops, images[0])
+                and images[0].shape == images[1].shape and images[0].dtype == images[1].dtype == torch.float32
+                and images[0].device == images[1].device)
+        stack = images[0] if len(images) == 1 else tuple(images) if pair else torch.cat(images, 0)
+        if position is not None:
+            return self.backbone(stack, ops, input_norm, out_addend=position)[::-1]
         return self.backbone(stack, ops, input_norm)[::-1]              # low -> high resolution
 
     def _match(self, feats, nb, attn_type='', attn_splits_list=None, corr_radius_list=None, prop_radius_list=None, num_reg_refine=1,
                pred_bidir_flow=False, task='flow', intrinsics=None, pose=None, min_depth=1. / 0.5, max_depth=1. / 10,
-               num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False):
+               num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, stream_has_pos=False, pred_out=None):
         """The match step: everything after the encoder, on per-scale features ``feats[s] = [f0; f1]`` (``[2 nb, C, h, w]``, the
-        first images of the ``nb`` pairs, then the second ones)."""
+        first images of the ``nb`` pairs, then the second ones).  ``stream_has_pos``: the encoder added the position table already
+        (``_forward_one`` decides; one scale, no refinement).  ``pred_out``: see ``_forward_one``."""
         ops = self.ops
         dev = feats[0].device
         flow, pred = None, None
@@ -773,8 +802,9 @@ class UniMatch(nn.Module):
             if tok1 is ori1 and both is not None:
                 # no warp, no bidirectional stacking: the stream [f0; f1] is the encoder's output -- one position add on
                 # the whole of it instead of two adds and a concatenation
-                tok0, tok1 = self.transformer(ops, None, None, h, w, attn_type, splits, stream=both + pos)
+                tok0, tok1 = self.transformer(ops, None, None, h, w, attn_type, splits, stream=both if stream_has_pos else both + pos)
             else:
+                assert not stream_has_pos
                 tok0, tok1 = self.transformer(ops, ori0 + pos, tok1 + pos, h, w, attn_type, splits)
             if self.debug_taps is not None:
                 self.debug_taps[f'f0_s{s}'], self.debug_taps[f'f1_s{s}'] = _to_map(tok0, h, w), _to_map(tok1, h, w)
@@ -834,7 +864,7 @@ class UniMatch(nn.Module):
                     pad = torch.cat([flow, torch.zeros_like(flow)], 1)
                     pred = self._upsample(pad, f0_map, is_depth=True).clamp(min=min_depth, max=max_depth)[:, :1]
                 else:
-                    pred = self._upsample(flow, f0_map)
+                    pred = self._upsample(flow, f0_map, out=pred_out)
                 continue
             assert num_reg_refine > 0
             pose_r = pose
@@ -879,7 +909,8 @@ class UniMatch(nn.Module):
                         pred = self._upsample(pad, f0_map, is_depth=True).clamp(
                             min=min_depth, max=max_depth)[:, :1]
                     elif nhwc is not None:
-                        pred = ops.convex_upsample(flow, up_mask, self.upsample_factor, False, mask_nhwc=True)
+                        pred = ops.convex_upsample(flow, up_mask, self.upsample_factor, False, mask_nhwc=True,
+                                                   out=pred_out if task == 'flow' and not pred_bidir_flow else None)
                     else:
                         pred = self._convex(flow, up_mask)
         if task == 'stereo':

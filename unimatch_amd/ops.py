@@ -156,6 +156,10 @@ class HipOps(WorkspaceRegistry):
     norm_on_load = True        # ... a residual block's middle InstanceNorm + ReLU inside its second convolution (um_conv2d_norm_fwd)
     fused_entry = True         # ... a stride-2 block's input apply, first convolution and projection shortcut in one launch (um_conv2d_entry_fwd),
                                #     and the projection's own InstanceNorm inside the block's output apply (um_nhwc_instance_norm_sc)
+    fused_glue = True          # no copy / add / format pass between neighbouring kernels: the stem reads the two image tensors of a pair batch
+                               #     (um_stem_conv_pair_fwd), the encoder's last convolution adds the position table (um_conv2d_addend_fwd), the
+                               #     upsampler head's input is one launch (um_nhwc_concat_planes) and its hidden map stays operand planes, the
+                               #     parts of a batch write into one prediction (convex_upsample(out=))
     CONV_MODE = 0              # ... always in the exact arithmetic: 'fast' (bf16) is a property of the matching path only
     WSHIFT = 10                # weights are scaled by 2^10 before the fp16 split (exact), see linear.hip
 
@@ -460,15 +464,22 @@ class HipOps(WorkspaceRegistry):
         return out
 
     # ------------------------------------------------------------------ convex upsampling (SURVEY 8(f) "next" row)
-    def convex_upsample(self, flow, mask, factor, is_depth=False, mask_nhwc=False):
+    def convex_upsample(self, flow, mask, factor, is_depth=False, mask_nhwc=False, out=None):
         """RAFT convex upsampling of ``flow [B,V,h,w]`` with ``mask [B,9*factor^2,h,w]`` (or NHWC ``[B*h*w, 9*factor^2]``
-        with ``mask_nhwc``) -> ``[B,V,factor*h,factor*w]``."""
+        with ``mask_nhwc``) -> ``[B,V,factor*h,factor*w]``.  ``out``: the destination, a contiguous fp32 tensor of that shape on the
+        flow's device (a batch slice of a bigger prediction); it is what the call returns."""
         b, v, h, w = flow.shape
         want = (b * h * w, 9 * factor * factor) if mask_nhwc else (b, 9 * factor * factor, h, w)
         if not (flow.is_cuda and flow.dtype == torch.float32 and mask.dtype == torch.float32 and tuple(mask.shape) == want):
             raise ValueError(f'convex_upsample: bad shapes flow {tuple(flow.shape)} mask {tuple(mask.shape)}')
         flow, mask = flow.contiguous(), mask.contiguous()
-        up = torch.empty((b, v, factor * h, factor * w), dtype=torch.float32, device=flow.device)
+        up = out
+        if up is None:
+            up = torch.empty((b, v, factor * h, factor * w), dtype=torch.float32, device=flow.device)
+        elif not (tuple(up.shape) == (b, v, factor * h, factor * w) and up.dtype == torch.float32 and up.device == flow.device
+                  and up.is_contiguous()):
+            raise ValueError(f'convex_upsample: out must be a contiguous float32 [{b}, {v}, {factor * h}, {factor * w}] tensor on '
+                             f'{flow.device}, got {tuple(up.shape)} {up.dtype} {up.device}')
         code = self._launch('convex_upsample', lambda: self.lib.um_convex_upsample(
             _ptr(flow), _ptr(mask), _ptr(up), b, v, h, w, factor, int(bool(is_depth)), int(bool(mask_nhwc)), _stream()))
         _abi.check(code, 'um_convex_upsample')
@@ -702,8 +713,10 @@ class HipOps(WorkspaceRegistry):
                    'um_weight_planes')
         return self._cache_put(key, (weight,), (planes, cout, cin, kh, kw))
 
-    def conv2d_nhwc(self, act, weight, bias=None, stride=1, padding=(1, 1), relu=False, stats=False):
-        """``act``: ``(planes, b, h, w, cin)``; returns fp32 ``[b*ho*wo, cout]`` and ``(ho, wo)``.  With ``stats`` the epilogue also emits the per-tile InstanceNorm statistics: ``self.last_conv_stats``."""
+    def conv2d_nhwc(self, act, weight, bias=None, stride=1, padding=(1, 1), relu=False, stats=False, image_addend=None):
+        """``act``: ``(planes, b, h, w, cin)``; returns fp32 ``[b*ho*wo, cout]`` and ``(ho, wo)``.  With ``stats`` the epilogue also emits the per-tile InstanceNorm statistics: ``self.last_conv_stats``.
+        ``image_addend``: fp32 ``[ho*wo, cout]``, one table added to every image's output in the epilogue (``um_conv2d_addend_fwd``,
+        periodic form): bit for bit the plain result ``+ image_addend.repeat(b, 1)``; excludes ``relu`` and ``stats``."""
         planes, b, h, w, cin = act
         wp, cout, wcin, kh, kw = self.conv_weight_planes(weight)
         if wcin != cin:
@@ -718,6 +731,18 @@ class HipOps(WorkspaceRegistry):
                                                 device=planes.device), parts)
         st = self.last_conv_stats[0] if self.last_conv_stats is not None else None
         meta = {'flops': 2.0 * b * ho * wo * cout * kh * kw * cin}
+        if image_addend is not None:
+            if relu or stats:
+                raise ValueError('conv2d_nhwc: image_addend excludes relu and stats')
+            if not (image_addend.is_cuda and image_addend.dtype == torch.float32 and image_addend.is_contiguous()
+                    and tuple(image_addend.shape) == (ho * wo, cout)):
+                raise ValueError(f'conv2d_nhwc: image_addend must be a contiguous CUDA float32 [{ho * wo}, {cout}] tensor, got '
+                                 f'{tuple(image_addend.shape)} {image_addend.dtype}')
+            code = self._launch('conv', lambda: self.lib.um_conv2d_addend_fwd(
+                _ptr(planes), _ptr(wp), _ptr(bias) if bias is not None else None, _ptr(image_addend), cout, 1, _ptr(out),
+                b, h, w, cin, cout, kh, kw, stride, ph, pw, self.WSHIFT, self.CONV_MODE, _stream()), meta)
+            _abi.check(code, 'um_conv2d_addend_fwd')
+            return out, ho, wo
         code = self._launch('conv', lambda: self.lib.um_conv2d_fwd(
             _ptr(planes), _ptr(wp), _ptr(bias) if bias is not None else None, _ptr(out), _ptr(st) if st is not None else None,
             b, h, w, cin, cout, kh, kw,
@@ -812,6 +837,25 @@ class HipOps(WorkspaceRegistry):
             pieces = list(pieces) + [torch.zeros((rows, cp - c), dtype=torch.float32, device=pieces[0].device)]
         x = pieces[0].contiguous() if len(pieces) == 1 else torch.cat(list(pieces), 1)
         planes, _ = self.nhwc_norm(x, 1, rows, normalize=False, relu=False, want_planes=True)
+        return planes, cp
+
+    def nhwc_concat_planes(self, flow, tokens, pad_to=32):
+        """``nhwc_planes_from([flow.permute(0, 2, 3, 1).reshape(rows, V), tokens])`` in one launch (``um_nhwc_concat_planes``): ``flow``
+        fp32 ``[b, V, h, w]`` (V <= 4), ``tokens`` fp32 ``[b*h*w, C]`` -> ``(planes, channels)``, the same bytes."""
+        if pad_to != 32:
+            raise ValueError('nhwc_concat_planes: the kernel pads to 32 channels')
+        b, v, h, w = flow.shape
+        rows = b * h * w
+        self._check_rows('tokens', tokens, tokens.shape[1])
+        if not (flow.is_cuda and flow.dtype == torch.float32 and flow.is_contiguous() and tokens.shape[0] == rows):
+            raise ValueError(f'nhwc_concat_planes: expected a contiguous CUDA float32 flow [b, V, h, w] and tokens [b*h*w, C], got '
+                             f'{tuple(flow.shape)} {flow.dtype} and {tuple(tokens.shape)}')
+        c = tokens.shape[1]
+        cp = (v + c + 31) // 32 * 32
+        planes = torch.empty(self.lib.um_planes_bytes(rows + 1, cp, self.CONV_MODE), dtype=torch.uint8, device=flow.device)
+        code = self._launch('instance_norm', lambda: self.lib.um_nhwc_concat_planes(
+            _ptr(flow), _ptr(tokens), _ptr(planes), b, h * w, v, c, self.CONV_MODE, _stream()))
+        _abi.check(code, 'um_nhwc_concat_planes')
         return planes, cp
 
     def conv_weight_padded(self, weight, cin_to):
@@ -984,13 +1028,26 @@ class HipOps(WorkspaceRegistry):
 
     def stem_conv(self, image, weight, norm_mean_std=None, stats=True):
         """The encoder's 7x7/2 stem on ``um_stem_conv_fwd``: fp32 NCHW image ``[b,3,h,w]`` -> fp32 NHWC ``[b*ho*wo, cout]``.
-        ``norm_mean_std``: ``((m0,m1,m2), (s0,s1,s2))`` applies the reference's ``(x / 255 - mean) / std`` while packing."""
+        ``norm_mean_std``: ``((m0,m1,m2), (s0,s1,s2))`` applies the reference's ``(x / 255 - mean) / std`` while packing.
+        ``image`` may be a tuple of two such tensors of one size: the stem of their concatenation, which is never built
+        (``um_stem_conv_pair_fwd``)."""
+        pair = None
+        if isinstance(image, (tuple, list)):
+            pair = tuple(image)
+            if len(pair) != 2 or pair[0].shape[1:] != pair[1].shape[1:] or pair[0].device != pair[1].device:
+                raise ValueError('stem_conv: a tuple holds two image tensors of one size on one device')
+            for im in pair[1:]:
+                if not (im.is_cuda and im.dtype == torch.float32 and im.dim() == 4 and im.shape[1] == 3 and im.is_contiguous()):
+                    raise ValueError('stem_conv: expected a contiguous CUDA float32 [b, 3, h, w] image')
+            image = pair[0]
         if not (image.is_cuda and image.dtype == torch.float32 and image.dim() == 4 and image.shape[1] == 3
                 and image.is_contiguous()):
             raise ValueError('stem_conv: expected a contiguous CUDA float32 [b, 3, h, w] image')
         if tuple(weight.shape[1:]) != (3, 7, 7):
             raise ValueError('stem_conv: expected a [cout, 3, 7, 7] weight')
         b, _, h, w = image.shape
+        if pair is not None:
+            b += pair[1].shape[0]
         cout = weight.shape[0]
         key, hit = self._cache_get('stem', (weight,))
         if hit is None:
@@ -1015,10 +1072,16 @@ class HipOps(WorkspaceRegistry):
             std = (ctypes.c_float * 3)(*[float(v) for v in norm_mean_std[1]])
         else:
             mean = std = None
+        meta = {'flops': 2.0 * b * ho * wo * cout * 147}
+        if pair is not None:
+            code = self._launch('conv', lambda: self.lib.um_stem_conv_pair_fwd(
+                _ptr(pair[0]), pair[0].shape[0], _ptr(pair[1]), pair[1].shape[0], int(norm_mean_std is not None), mean, std,
+                _ptr(scratch), _ptr(hit), _ptr(out), _ptr(st) if st is not None else None, h, w, cout, self.WSHIFT, _stream()), meta)
+            _abi.check(code, 'um_stem_conv_pair_fwd')
+            return out, ho, wo
         code = self._launch('conv', lambda: self.lib.um_stem_conv_fwd(
             _ptr(image), int(norm_mean_std is not None), mean, std, _ptr(scratch), _ptr(hit), _ptr(out),
-            _ptr(st) if st is not None else None, b, h, w, cout, self.WSHIFT, _stream()),
-            {'flops': 2.0 * b * ho * wo * cout * 147})
+            _ptr(st) if st is not None else None, b, h, w, cout, self.WSHIFT, _stream()), meta)
         _abi.check(code, 'um_stem_conv_fwd')
         return out, ho, wo
 

@@ -89,19 +89,30 @@ class PartRunner:
                               tuple(v) if isinstance(v, (list, tuple)) else tuple(v.shape)) for k, v in kw.items()))
         return (n, tuple(geometry), str(device), small, version)
 
-    def run_parts(self, model, n, batch, bidir, geometry, device, kw, prepare, compute):
+    def run_parts(self, model, n, batch, bidir, geometry, device, kw, prepare, compute, out_shape=None):
         """Part ``r`` of ``n`` (sample range ``shard_bounds(batch, r, n)``) is ``compute(r, prepare(r))`` -> its list of predictions
         ``[bidir * b_r, ...]``.  ``prepare`` runs on the caller's stream before any side stream is released (the parts' inputs),
         ``compute`` on the part's stream, inside the backend's ``part_scope(r)``; ``geometry``, ``device`` and the keyword arguments
         ``kw`` identify the call for the first-call-sequential rule.  The predictions are joined in the reference's [forward;
-        backward] order."""
+        backward] order.
+
+        ``out_shape = (batch, ...)`` (``bidir == 1`` only): the one prediction is allocated here, on the caller's stream, and part ``r``
+        is ``compute(r, prepare(r), out=<its sample range of it>)``.  Parts that return that very slice have written the joined
+        prediction already and nothing is concatenated; anything else a part returns is joined as before."""
         cuda = device.type == 'cuda'
+        # Allocated BEFORE the side streams wait on the caller's stream (below): the block belongs to the caller's pool, whatever wrote
+        # it there earlier is ordered before every part, and the caller's wait at the join orders the parts' writes before its readers.
+        # The prediction is kept alive by the caller, never by a side stream's pool.
+        full = slices = None
+        if out_shape is not None and bidir == 1 and cuda:
+            full = torch.empty(tuple(out_shape), dtype=torch.float32, device=device)
+            slices = [full[slice(*shard_bounds(batch, r, n))] for r in range(n)]
 
         def one(r, ins):
             if not cuda:
                 return compute(r, ins)
             with model.ops.part_scope(r):                           # a captured graph owns one set of scratch per part
-                return compute(r, ins)
+                return compute(r, ins) if slices is None else compute(r, ins, out=slices[r])
 
         key = self._key(model, n, geometry, device, kw)
         concurrent = cuda and key in self._seen and self._backend is not None and self._backend == self._backend_state(model)
@@ -127,6 +138,9 @@ class PartRunner:
                 for s in side:
                     cur.wait_stream(s)
         self._backend = self._backend_state(model)
+        if slices is not None and all(len(outs[r]) == 1 and outs[r][0] is slices[r] for r in range(n)):
+            # every part wrote its sample range of `full`: nothing of the side streams' pools was consumed, nothing to order behind
+            return {'flow_preds': [full]}
         # every prediction of the list: [bidir * b_r, ...] per part -> [bidir * batch, ...] in the reference's [forward; backward] order
         counts = [shard_bounds(batch, r, n)[1] - shard_bounds(batch, r, n)[0] for r in range(n)]
         preds = []
