@@ -637,6 +637,40 @@ int um_image_prepare(const void* src, int src_layout, float* dst, int batch, int
                      const float* std, int mode, int hp, int wp, int top, int left, void* stream);
 int um_pred_restore(const float* pred, float* out, int batch, int channels, int hp, int wp, int mode, int top, int left, int h, int w,
                     int kind, int transpose, void* stream);
+/* The same two launches with a horizontal mirror of image-space x as their LAST step, for the flipped views of the reference's
+ * stereo inference (evaluate_stereo.py:790-841: resize, then hflip; resize back and rescale, then hflip):
+ *   um_image_prepare_flip  hflip != 0: dst[..., x] = prepared[..., wp - 1 - x], `prepared` being what um_image_prepare writes.
+ *   um_pred_restore_flip   hflip != 0: out[..., x] = restored[..., w - 1 - x], `restored` being what um_pred_restore writes.
+ * The mirror is an index remap inside the one launch: the bilinear arithmetic is evaluated at the mirrored destination index, so the
+ * result is torch.flip(<unflipped result>, [-1]) bit for bit (a resize of a mirrored source would differ in fp32).  hflip == 0 is
+ * um_image_prepare / um_pred_restore, which delegate here. */
+int um_image_prepare_flip(const void* src, int src_layout, float* dst, int batch, int h, int w, int transpose, const float* mean,
+                          const float* std, int mode, int hp, int wp, int top, int left, int hflip, void* stream);
+int um_pred_restore_flip(const float* pred, float* out, int batch, int channels, int hp, int wp, int mode, int top, int left, int h,
+                         int w, int kind, int transpose, int hflip, void* stream);
+
+/* Scalar map -> colour image (csrc/visualize.hip): the reference's vis_disparity and viz_depth_tensor (utils/visualization.py:11-16,
+ * 92-107) per image of a batch.  x [B,h,w] fp32 -> rgb [B,h,w,3] uint8 = lut[idx], lut a DEVICE table [256][3]; stats_out (device,
+ * may be NULL) receives [B][2] = vmin, vmax.  All arithmetic on values is fp32, every operation rounded on its own, IEEE division:
+ *   v = inverse != 0 ? 1.0f / x : x;  vmin = the image's minimum of v.
+ *   UM_NORM_MINMAX_255   vmax = the image's maximum; idx = (uint8) trunc(((v - vmin) / (vmax - vmin)) * 255.0f).
+ *   UM_NORM_MIN_P95_256  vmax = the 95th percentile, linear: k = 0.95 (n - 1) in float64, lo = floor(k), hi = min(lo + 1, n - 1),
+ *                        t = k - lo, vmax = (float)((double)a[lo] + ((double)a[hi] - (double)a[lo]) * t) with a the EXACT order
+ *                        statistics of v (a radix select over order-preserving keys: a[lo], a[hi] are elements of the input whatever
+ *                        the distribution); xa = ((v - vmin) / (vmax - vmin)) * 256.0f; idx = 255 if xa >= 256, else trunc(xa)
+ *                        clamped to 0..255; idx = 0 for the whole image if vmax == vmin.
+ * NaN or infinite values of v are outside the reference contract (NumPy's own result then depends on its version): the call
+ * terminates, stays in bounds and gives a pixel whose normalised value is NaN index 0 (so a constant image under
+ * UM_NORM_MINMAX_255 is all index 0); nothing more is promised for them.
+ * Launches: per radix digit (11, 11, 10 bits) one histogram launch (LDS histograms, one partial per workgroup into `workspace`)
+ * and one fold per image in index order, then the colour launch; UM_NORM_MINMAX_255 needs the first pair only, without a histogram.
+ * No global atomics, no counters; every workspace slot that is read was written by the same call.  workspace (8-byte aligned) >=
+ * um_scalar_to_rgb_workspace_bytes(batch, h, w) (0 for bad sizes); batch <= 65535, h * w <= 2^30. */
+#define UM_NORM_MINMAX_255 0  /* vis_disparity */
+#define UM_NORM_MIN_P95_256 1 /* viz_depth_tensor */
+size_t um_scalar_to_rgb_workspace_bytes(int batch, int h, int w);
+int um_scalar_to_rgb(const float* x, unsigned char* rgb, int batch, int h, int w, int inverse, int norm, const unsigned char* lut,
+                     float* stats_out, void* workspace, size_t ws_bytes, void* stream);
 
 /* The per-scale loop's small glue ops (round 3: they were torch calls):
  *   um_flow_upsample2x  out[B,V,2h,2w] = mult * bilinear_up2(flow[B,V,h,w]), align_corners = True -- unimatch/unimatch.py:162-163

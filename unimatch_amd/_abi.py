@@ -90,6 +90,11 @@ SIGNATURES = {
     'um_image_prepare': (_c_int, [_c_void_p, _c_int, _c_void_p] + [_c_int] * 4 + [ctypes.POINTER(ctypes.c_float)] * 2 + [_c_int] * 5 +
                          [_c_void_p]),
     'um_pred_restore': (_c_int, [_c_void_p] * 2 + [_c_int] * 11 + [_c_void_p]),
+    'um_image_prepare_flip': (_c_int, [_c_void_p, _c_int, _c_void_p] + [_c_int] * 4 + [ctypes.POINTER(ctypes.c_float)] * 2 + [_c_int] * 6 +
+                              [_c_void_p]),
+    'um_pred_restore_flip': (_c_int, [_c_void_p] * 2 + [_c_int] * 12 + [_c_void_p]),
+    'um_scalar_to_rgb_workspace_bytes': (_c_size_t, [_c_int] * 3),
+    'um_scalar_to_rgb': (_c_int, [_c_void_p] * 2 + [_c_int] * 5 + [_c_void_p] * 3 + [_c_size_t, _c_void_p]),
     'um_convex_upsample': (_c_int, [_c_void_p] * 3 + [_c_int] * 7 + [_c_void_p]),
     'um_flow_upsample2x': (_c_int, [_c_void_p] * 2 + [_c_int] * 4 + [ctypes.c_float, _c_void_p]),
     'um_depth_cam_pack': (_c_int, [_c_void_p] * 3 + [_c_int, ctypes.c_float, _c_int, _c_void_p]),

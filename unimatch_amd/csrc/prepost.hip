@@ -8,6 +8,10 @@
 //   um_pred_restore    prediction [B,C,hp,wp] -> [B,C,h,w]: crop at (top, left) or bilinear resize, the per-kind rescale of the
 //                      resize path ((v * ori) / inf), optional transpose back (the flow channels are NOT swapped, as in the reference).
 //
+//   um_image_prepare_flip / um_pred_restore_flip   the same launches with a mirror of image-space x as the last step (the flipped
+//                      views of the reference's stereo inference, evaluate_stereo.py:790-841): an index remap, evaluated with the
+//                      mirrored column's arithmetic, so the result is torch.flip of the unflipped one bit for bit.
+//
 // Both are memory-bound, one launch each, and keep no state.  "Image space" below is the frame after the optional transpose
 // (ih x iw): all geometry is expressed there.  Thread mapping:
 //   plain       a thread produces VEC (4 or 1) consecutive output pixels of one row and stores them with one 16-byte (4-byte) store
@@ -58,6 +62,7 @@ struct PrepArgs {
     int h, w;              // stored size of a source image
     int hp, wp;
     int tr, norm;
+    int flip;              // mirror image-space x: dst[..., x] = prepared[..., wp - 1 - x]
     float mean[3], std[3];
     PPGeom g;
 };
@@ -84,9 +89,11 @@ __device__ __forceinline__ void prep_fetch(const PrepArgs& a, int b, int y, int 
     }
 }
 
+// (ox is the STORED column: with the mirror the pixel computed is the one of column wp - 1 - ox, with that column's arithmetic)
 template <int LAYOUT>
 __device__ __forceinline__ void prep_pixel(const PrepArgs& a, int b, int oy, int ox, float out[3]) {
     const PPGeom& g = a.g;
+    ox = a.flip ? a.wp - 1 - ox : ox;
     if (g.mode == UM_SIZE_PAD) {
         prep_fetch<LAYOUT>(a, b, min(max(oy - g.top, 0), g.ih - 1), min(max(ox - g.left, 0), g.iw - 1), out);
         return;
@@ -185,8 +192,9 @@ static inline bool pp_size_ok(int batch, int channels, int h, int w, int hp, int
            (long)h * w <= (1L << 28) && (long)hp * wp <= (1L << 28);
 }
 
-extern "C" int um_image_prepare(const void* src, int src_layout, float* dst, int batch, int h, int w, int transpose, const float* mean,
-                                const float* std, int mode, int hp, int wp, int top, int left, void* stream_) {
+extern "C" int um_image_prepare_flip(const void* src, int src_layout, float* dst, int batch, int h, int w, int transpose,
+                                     const float* mean, const float* std, int mode, int hp, int wp, int top, int left, int hflip,
+                                     void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     bool ok = src && dst && pp_size_ok(batch, 3, h, w, hp, wp) && (src_layout == UM_IMG_F32_NCHW || src_layout == UM_IMG_U8_NHWC) &&
               (mode == UM_SIZE_PAD || mode == UM_SIZE_RESIZE) && ((mean == nullptr) == (std == nullptr));
@@ -208,6 +216,7 @@ extern "C" int um_image_prepare(const void* src, int src_layout, float* dst, int
     a.wp = wp;
     a.tr = transpose ? 1 : 0;
     a.norm = mean ? 1 : 0;
+    a.flip = hflip ? 1 : 0;
     for (int c = 0; c < 3; ++c) {
         a.mean[c] = mean ? mean[c] : 0.0f;
         a.std[c] = std ? std[c] : 1.0f;
@@ -245,6 +254,7 @@ struct RestArgs {
     int channels, hp, wp;
     int h, w;              // stored size of an output plane
     int scaled;            // resize path of a flow / disparity: (v * mul[c]) / div[c]
+    int flip;              // mirror the stored x: out[..., x] = restored[..., w - 1 - x]
     float mul[2], div[2];
     PPGeom g;              // ih, iw: the PREDICTION's size (hp, wp); the output in image space is rh x rw
 };
@@ -273,10 +283,10 @@ __global__ __launch_bounds__(256) void pred_restore_kernel(RestArgs a) {
     if (VEC == 4) {                             // host: w % 4 == 0 and out 16-byte aligned
         f32x4 r;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = rest_pixel(a, z, c, y, x0 + i);
+        for (int i = 0; i < 4; ++i) r[i] = rest_pixel(a, z, c, y, a.flip ? a.w - 1 - (x0 + i) : x0 + i);
         *reinterpret_cast<f32x4*>(o) = r;
     } else {
-        o[0] = rest_pixel(a, z, c, y, x0);
+        o[0] = rest_pixel(a, z, c, y, a.flip ? a.w - 1 - x0 : x0);
     }
 }
 
@@ -290,15 +300,20 @@ __global__ __launch_bounds__(256) void pred_restore_tr_kernel(RestArgs a, int ve
     for (int k = 0; k < 4; ++k) {
         const int j = j0 + 8 * k;
         const int oy = ty0 + i, ox = tx0 + j;
-        if (oy < a.h && ox < a.w) tile[0][j][i] = rest_pixel(a, z, c, ox, oy);
+        if (oy < a.h && ox < a.w) tile[0][j][i] = rest_pixel(a, z, c, a.flip ? a.w - 1 - ox : ox, oy);
     }
     __syncthreads();
     const long plane = (long)a.h * a.w;
     pp_store_tile<1>(tile, a.out + (long)z * plane, plane, a.h, a.w, ty0, tx0, vec);
 }
 
-extern "C" int um_pred_restore(const float* pred, float* out, int batch, int channels, int hp, int wp, int mode, int top, int left, int h,
-                               int w, int kind, int transpose, void* stream_) {
+extern "C" int um_image_prepare(const void* src, int src_layout, float* dst, int batch, int h, int w, int transpose, const float* mean,
+                                const float* std, int mode, int hp, int wp, int top, int left, void* stream) {
+    return um_image_prepare_flip(src, src_layout, dst, batch, h, w, transpose, mean, std, mode, hp, wp, top, left, 0, stream);
+}
+
+extern "C" int um_pred_restore_flip(const float* pred, float* out, int batch, int channels, int hp, int wp, int mode, int top, int left,
+                                    int h, int w, int kind, int transpose, int hflip, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     bool ok = pred && out && pp_size_ok(batch, channels, h, w, hp, wp) && (mode == UM_SIZE_PAD || mode == UM_SIZE_RESIZE) &&
               ((kind == UM_PRED_FLOW && channels == 2) || ((kind == UM_PRED_DISPARITY || kind == UM_PRED_DEPTH) && channels == 1));
@@ -318,6 +333,7 @@ extern "C" int um_pred_restore(const float* pred, float* out, int batch, int cha
     a.h = h;
     a.w = w;
     a.scaled = (mode == UM_SIZE_RESIZE && kind != UM_PRED_DEPTH) ? 1 : 0;
+    a.flip = hflip ? 1 : 0;
     a.mul[0] = (float)rw;                       // flow u and disparity: * W / wp;  flow v: * H / hp
     a.div[0] = (float)wp;
     a.mul[1] = (float)rh;
@@ -338,4 +354,9 @@ extern "C" int um_pred_restore(const float* pred, float* out, int batch, int cha
             hipLaunchKernelGGL(pred_restore_kernel<1>, grid, block, 0, stream, a);
     }
     return (int)hipGetLastError();
+}
+
+extern "C" int um_pred_restore(const float* pred, float* out, int batch, int channels, int hp, int wp, int mode, int top, int left, int h,
+                               int w, int kind, int transpose, void* stream) {
+    return um_pred_restore_flip(pred, out, batch, channels, hp, wp, mode, top, left, h, w, kind, transpose, 0, stream);
 }

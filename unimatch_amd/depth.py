@@ -1,0 +1,98 @@
+"""A posed-scene driver shaped like the reference's ``inference_depth`` (evaluate_depth.py:296-419).
+
+``python -m unimatch_amd.depth --scene DIR --out DIR [...]`` reads a ScanNet-layout scene -- ``color/*.jpg|png`` (sorted),
+``pose/*.txt`` (one 4 x 4 camera-to-world matrix per frame, sorted) and ``intrinsic/*.txt`` (a 4 x 4 file whose upper-left 3 x 3 is
+used) -- predicts the depth of every frame i from the pair (i, i + 1) with :meth:`UniMatch.predict` and writes ``<stem>.png``: the
+reference's ``viz_depth_tensor(1 / depth)`` colouring (:mod:`unimatch_amd.visualize`); with ``--pred-bidir-depth`` also
+``<stem>_bwd.png``, the depth of frame i + 1.  The relative pose is ``inv(pose_tgt) @ pose_ref`` in float32 on the host; the model
+searches the inverse depths ``1 / max_depth .. 1 / min_depth``.  Frames are uploaded as uint8 and normalised on the device; like the
+reference's runner this one RESIZES (to the next multiple of ``padding_factor`` or to ``inference_size``) and does NOT rescale the
+intrinsics; ``--scale-intrinsics`` opts into :meth:`InferenceGeometry.scaled_intrinsics`.  Reading frames needs PIL.
+"""
+import argparse
+import glob
+import os
+
+import numpy as np
+import torch
+
+from .stereo import load_model, nearest_size
+from .video import read_frame_u8
+from .visualize import inverse_depth_to_image
+
+
+def read_scene(scene_dir):
+    """``(image paths, poses [N, 4, 4] float32, intrinsics [3, 3] float32)`` of a ScanNet-layout scene."""
+    imgs = sorted(glob.glob(os.path.join(scene_dir, 'color', '*.jpg')) + glob.glob(os.path.join(scene_dir, 'color', '*.png')))
+    poses = sorted(glob.glob(os.path.join(scene_dir, 'pose', '*.txt')))
+    intr = sorted(glob.glob(os.path.join(scene_dir, 'intrinsic', '*.txt')))
+    if not intr:
+        raise FileNotFoundError(f'no intrinsic/*.txt under {scene_dir}')
+    if len(imgs) != len(poses):
+        raise ValueError(f'{len(imgs)} images and {len(poses)} poses under {scene_dir}')
+    k = np.loadtxt(intr[0]).astype(np.float32).reshape(4, 4)[:3, :3]
+    p = np.stack([np.loadtxt(f).astype(np.float32).reshape(4, 4) for f in poses], 0) if poses else np.zeros((0, 4, 4), np.float32)
+    return imgs, p, k
+
+
+def relative_pose(pose_ref, pose_tgt):
+    """``inv(pose_tgt) @ pose_ref`` in float32 (evaluate_depth.py:347-350)."""
+    return (np.linalg.inv(pose_tgt.astype(np.float32)) @ pose_ref.astype(np.float32)).astype(np.float32)
+
+
+def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_size=None, min_depth=0.5, max_depth=10.,
+              num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, scale_intrinsics=False, device='cuda'):
+    """``inference_depth`` over the scene: returns the number of frames written (one less than the scene has)."""
+    from .io import write_png8
+    from .prepost import InferenceGeometry
+    imgs, poses, k = read_scene(scene_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    skip = ('task', 'min_depth', 'max_depth', 'num_depth_candidates', 'depth_from_argmax', 'pred_bidir_depth', 'intrinsics', 'pose')
+    fwd_kw = {key: v for key, v in fwd_kw.items() if key not in skip}
+    for i in range(len(imgs) - 1):
+        ref, tgt = read_frame_u8(imgs[i])[None].to(device), read_frame_u8(imgs[i + 1])[None].to(device)
+        size = tuple(inference_size) if inference_size else nearest_size(ref.shape[1:3], padding_factor)
+        intrinsics = torch.from_numpy(k)[None].to(device)
+        if scale_intrinsics:
+            intrinsics = InferenceGeometry.resized(ref.shape[1:3], size).scaled_intrinsics(intrinsics)
+        pose = torch.from_numpy(relative_pose(poses[i], poses[i + 1]))[None].to(device)
+        with torch.no_grad():
+            depth = model.predict(ref, tgt, inference_size=size, task='depth', intrinsics=intrinsics, pose=pose,
+                                  min_depth=1. / max_depth, max_depth=1. / min_depth, num_depth_candidates=num_depth_candidates,
+                                  depth_from_argmax=depth_from_argmax, pred_bidir_depth=pred_bidir_depth, **fwd_kw)['flow_preds'][-1]
+        rgb = inverse_depth_to_image(depth).cpu().numpy()                                    # [1 or 2, H, W, 3]
+        stem = os.path.join(out_dir, os.path.splitext(os.path.basename(imgs[i]))[0])
+        write_png8(stem + '.png', rgb[0])
+        if pred_bidir_depth:
+            write_png8(stem + '_bwd.png', rgb[1])
+    return max(0, len(imgs) - 1)
+
+
+def main(argv=None):
+    from .synth import CONFIGS
+    ap = argparse.ArgumentParser(description='depth of a posed ScanNet-layout scene (UniMatch.predict), coloured on the device')
+    ap.add_argument('--scene', required=True, help='directory with color/, pose/ and intrinsic/')
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--inference-size', type=int, nargs=2, default=None, metavar=('H', 'W'))
+    ap.add_argument('--padding-factor', type=int, default=16)
+    ap.add_argument('--min-depth', type=float, default=0.5)
+    ap.add_argument('--max-depth', type=float, default=10.)
+    ap.add_argument('--num-depth-candidates', type=int, default=64)
+    ap.add_argument('--depth-from-argmax', action='store_true')
+    ap.add_argument('--pred-bidir-depth', action='store_true')
+    ap.add_argument('--scale-intrinsics', action='store_true', help='rescale the intrinsics with the resize (the reference does not)')
+    ap.add_argument('--model-config', default='gmdepth_s1', choices=[k for k, v in CONFIGS.items() if v[1].get('task') == 'depth'])
+    ap.add_argument('--weights', default=None, help="checkpoint (the reference's: a state_dict, or {'model': state_dict}); "
+                                                    'default: the seeded synthetic weights')
+    ap.add_argument('--precision', default='exact', choices=['exact', 'fast'])
+    args = ap.parse_args(argv)
+    model, fwd_kw = load_model(args.model_config, args.weights, args.precision)
+    n = run_depth(model, args.scene, args.out, fwd_kw, padding_factor=args.padding_factor, inference_size=args.inference_size,
+                  min_depth=args.min_depth, max_depth=args.max_depth, num_depth_candidates=args.num_depth_candidates,
+                  depth_from_argmax=args.depth_from_argmax, pred_bidir_depth=args.pred_bidir_depth,
+                  scale_intrinsics=args.scale_intrinsics)
+    print(f'{n} frames written to {args.out}')
+
+
+if __name__ == '__main__':
+    main()

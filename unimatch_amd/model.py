@@ -484,7 +484,7 @@ class UniMatch(nn.Module):
     _PREDICT_DEFAULTS = {'flow': (8, 'sintel', 'flow'), 'stereo': (32, 'sintel', 'disparity'), 'depth': (16, 'kitti', 'depth')}
 
     def predict(self, img0, img1, *, inference_size=None, padding_factor=None, pad_mode=None, transpose='auto', normalize=None,
-                **forward_kw):
+                pred_right_disp=False, pred_bidir_disp=False, **forward_kw):
         """:meth:`forward` at an inference size, with the prediction back at the images' size: the block the reference's scripts
         repeat around the model (evaluate_flow.py:713-758, evaluate_stereo.py:340-375, evaluate_depth.py:78-129) through
         :class:`unimatch_amd.prepost.InferenceGeometry`.  Returns the forward's dict with ``flow_preds[-1]`` restored.
@@ -496,7 +496,15 @@ class UniMatch(nn.Module):
         pair has no transposed meaning); the flow channels are not swapped back, as in the reference.  ``normalize``: ``None``
         means ``task != 'flow'`` for uint8 input (the ImageNet constants) and ``False`` for fp32 input, which the stereo and depth
         loaders have normalised already; flow is always normalised inside the model.  ``forward_kw`` goes to :meth:`forward`.
-        On the GPU this adds three launches to the forward and never waits for the device."""
+        On the GPU this adds three launches to the forward and never waits for the device.
+
+        Stereo views (``task='stereo'`` only, else ``ValueError``; evaluate_stereo.py:790-841; consumed here, not passed on):
+        ``pred_right_disp`` runs the model on ``(hflip(right), hflip(left))`` and mirrors the restored disparity back: the right
+        view's disparity.  ``pred_bidir_disp`` runs ONE forward of batch 2B on ``[left; hflip(right)]``, ``[right; hflip(left)]`` and
+        returns ``flow_preds[-1]`` ``[2B, H, W]``: the left view's disparities, then the right view's, mirrored back (the reference
+        leaves that last mirror to its caller).  Both together follow the reference literally -- the doubling first, then the swap
+        -- so the halves come out in the other order.  The mirrors are part of the prepare / restore launches (four prepares into
+        the halves of two preallocated tensors, two restores into the halves of one): no ``torch.flip``, no ``torch.cat``."""
         from .prepost import InferenceGeometry, geometry_for, image_size
         task = forward_kw.get('task', 'flow')
         if task not in self._PREDICT_DEFAULTS:
@@ -510,10 +518,44 @@ class UniMatch(nn.Module):
         geom = geometry_for(shape, inference_size, padding_factor or factor, pad_mode or mode, transpose)
         if normalize is None:
             normalize = img0.dtype == torch.uint8 and task != 'flow'
+        if pred_right_disp or pred_bidir_disp:
+            if task != 'stereo':
+                raise ValueError(f"pred_right_disp / pred_bidir_disp are stereo views: task='stereo', got {task!r}")
+            return self._predict_stereo_views(img0, img1, geom, normalize, bool(pred_right_disp), bool(pred_bidir_disp), forward_kw)
         a0, a1 = geom.prepare(img0, img1, normalize=normalize)
         out = dict(self(a0, a1, **forward_kw))
         preds = list(out['flow_preds'])
         preds[-1] = geom.restore(preds[-1], kind)
+        out['flow_preds'] = preds
+        return out
+
+    def _predict_stereo_views(self, left, right, geom, normalize, right_disp, bidir, forward_kw):
+        """The flipped / doubled stereo views of :meth:`predict`.  With L, R the prepared views and ' the mirror, the model sees
+        right only ``(R', L')``; bidir only ``([L; R'], [R; L'])``; both ``([R'; L], [L'; R])`` (the doubled pair, swapped and
+        mirrored).  On the way back a half is mirrored iff the model's first image of that half was a mirrored view."""
+        if not bidir:
+            a0, = geom.prepare(right, normalize=normalize, hflip=True)
+            a1, = geom.prepare(left, normalize=normalize, hflip=True)
+            out = dict(self(a0, a1, **forward_kw))
+            preds = list(out['flow_preds'])
+            preds[-1] = geom.restore(preds[-1], 'disparity', hflip=True)
+            out['flow_preds'] = preds
+            return out
+        b = left.shape[0]
+        a0 = torch.empty((2 * b, 3) + geom.size, dtype=torch.float32, device=left.device)
+        a1 = torch.empty_like(a0)
+        plain, mirrored = (slice(b, None), slice(0, b)) if right_disp else (slice(0, b), slice(b, None))
+        geom.prepare(left, normalize=normalize, out=a0[plain])
+        geom.prepare(right, normalize=normalize, out=a1[plain])
+        geom.prepare(right, normalize=normalize, hflip=True, out=a0[mirrored])
+        geom.prepare(left, normalize=normalize, hflip=True, out=a1[mirrored])
+        out = dict(self(a0, a1, **forward_kw))
+        preds = list(out['flow_preds'])
+        pred = preds[-1]
+        back = torch.empty((2 * b,) + geom.shape, dtype=torch.float32, device=pred.device)
+        geom.restore(pred[plain], 'disparity', out=back[plain])
+        geom.restore(pred[mirrored], 'disparity', hflip=True, out=back[mirrored])
+        preds[-1] = back
         out['flow_preds'] = preds
         return out
 

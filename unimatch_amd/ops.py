@@ -538,11 +538,13 @@ class HipOps(WorkspaceRegistry):
             raise ValueError(f'{name}: the inference size {hp}x{wp} is empty')
         return (1 if mode == 'resize' else 0), hp, wp, top, left
 
-    def image_prepare(self, images, size, mode='pad', crop=(0, 0), transpose=False, mean=None, std=None):
+    def image_prepare(self, images, size, mode='pad', crop=(0, 0), transpose=False, mean=None, std=None, hflip=False, out=None):
         """``um_image_prepare``: ``images`` -- fp32 ``[B, 3, H, W]`` or uint8 ``[B, H, W, 3]`` -- to the model's input ``[B, 3, hp,
         wp]`` fp32 with ``size = (hp, wp)``: optional transpose, ``(x / 255 - mean) / std`` when ``mean`` / ``std`` (three floats each)
         are given, then ``mode='pad'`` (replicate padding, the image at ``crop = (top, left)``) or ``'resize'`` (bilinear,
-        align_corners).  Enqueued on the current stream: no synchronisation, no copy."""
+        align_corners), then ``hflip``: a mirror of x inside the same launch (``um_image_prepare_flip``), bit for bit ``torch.flip`` of the
+        unflipped result.  ``out``: a preallocated contiguous fp32 ``[B, 3, hp, wp]`` tensor (a batch slice of a larger one) to write
+        into.  Enqueued on the current stream: no synchronisation, no copy."""
         u8 = images.dtype == torch.uint8
         ok = images.is_cuda and images.dim() == 4 and (u8 or images.dtype == torch.float32) and images.shape[3 if u8 else 1] == 3
         if not ok:
@@ -557,18 +559,26 @@ class HipOps(WorkspaceRegistry):
         ih, iw = (w, h) if transpose else (h, w)
         if m == 0 and (top < 0 or left < 0 or top + ih > hp or left + iw > wp):
             raise ValueError(f'image_prepare: the image {ih}x{iw} at ({top}, {left}) leaves the padded size {hp}x{wp}')
-        out = torch.empty((b, 3, hp, wp), dtype=torch.float32, device=images.device)
+        if out is None:
+            out = torch.empty((b, 3, hp, wp), dtype=torch.float32, device=images.device)
+        elif not (out.is_cuda and out.device == images.device and out.dtype == torch.float32 and tuple(out.shape) == (b, 3, hp, wp)
+                  and out.is_contiguous()):
+            raise ValueError(f'image_prepare: out must be a contiguous CUDA float32 [{b}, 3, {hp}, {wp}] tensor on {images.device}, got '
+                             f'{tuple(out.shape)} {out.dtype} {out.device}')
         fmean = (ctypes.c_float * 3)(*mean) if mean is not None else None
         fstd = (ctypes.c_float * 3)(*std) if std is not None else None
-        code = self._launch('image_prepare', lambda: self.lib.um_image_prepare(
-            _ptr(images), 1 if u8 else 0, _ptr(out), b, h, w, int(bool(transpose)), fmean, fstd, m, hp, wp, top, left, _stream()))
-        _abi.check(code, 'um_image_prepare')
+        code = self._launch('image_prepare', lambda: self.lib.um_image_prepare_flip(
+            _ptr(images), 1 if u8 else 0, _ptr(out), b, h, w, int(bool(transpose)), fmean, fstd, m, hp, wp, top, left, int(bool(hflip)),
+            _stream()))
+        _abi.check(code, 'um_image_prepare_flip')
         return out
 
-    def pred_restore(self, pred, size, mode='pad', crop=(0, 0), kind='flow', transpose=False):
+    def pred_restore(self, pred, size, mode='pad', crop=(0, 0), kind='flow', transpose=False, hflip=False, out=None):
         """``um_pred_restore``: the prediction ``pred [B, C, hp, wp]`` back to the caller's frame ``size = (H, W)``: ``mode='pad'``
         crops at ``crop = (top, left)``, ``'resize'`` resizes and rescales by ``kind`` (``'flow'``: ``u * W / wp``, ``v * H / hp``;
-        ``'disparity'``: ``* W / wp``; ``'depth'``: nothing), then the optional transpose back (flow channels are not swapped)."""
+        ``'disparity'``: ``* W / wp``; ``'depth'``: nothing), then the optional transpose back (flow channels are not swapped), then
+        ``hflip``: a mirror of x inside the same launch (``um_pred_restore_flip``).  ``out``: a preallocated contiguous fp32
+        ``[B, C, H, W]`` tensor to write into."""
         kinds = {'flow': 0, 'disparity': 1, 'depth': 2}
         if kind not in kinds:
             raise ValueError(f'pred_restore: kind must be one of {sorted(kinds)}, got {kind!r}')
@@ -581,11 +591,42 @@ class HipOps(WorkspaceRegistry):
         ih, iw = (w, h) if transpose else (h, w)
         if m == 0 and (top < 0 or left < 0 or top + ih > hp or left + iw > wp):
             raise ValueError(f'pred_restore: the crop {ih}x{iw} at ({top}, {left}) leaves the prediction {hp}x{wp}')
-        out = torch.empty((b, c, h, w), dtype=torch.float32, device=pred.device)
-        code = self._launch('pred_restore', lambda: self.lib.um_pred_restore(
-            _ptr(pred), _ptr(out), b, c, hp, wp, m, top, left, h, w, kinds[kind], int(bool(transpose)), _stream()))
-        _abi.check(code, 'um_pred_restore')
+        if out is None:
+            out = torch.empty((b, c, h, w), dtype=torch.float32, device=pred.device)
+        elif not (out.is_cuda and out.device == pred.device and out.dtype == torch.float32 and tuple(out.shape) == (b, c, h, w)
+                  and out.is_contiguous()):
+            raise ValueError(f'pred_restore: out must be a contiguous CUDA float32 [{b}, {c}, {h}, {w}] tensor on {pred.device}, got '
+                             f'{tuple(out.shape)} {out.dtype} {out.device}')
+        code = self._launch('pred_restore', lambda: self.lib.um_pred_restore_flip(
+            _ptr(pred), _ptr(out), b, c, hp, wp, m, top, left, h, w, kinds[kind], int(bool(transpose)), int(bool(hflip)), _stream()))
+        _abi.check(code, 'um_pred_restore_flip')
         return out
+
+    # ------------------------------------------------------------------ colour maps of scalar predictions
+    NORMS = {'minmax_255': 0, 'min_p95_256': 1}
+
+    def scalar_to_rgb(self, x, lut, inverse=False, norm='minmax_255', return_stats=False):
+        """``um_scalar_to_rgb``: ``x [B, H, W]`` fp32 -> ``[B, H, W, 3]`` uint8 through the device table ``lut [256, 3]`` uint8, each
+        image normalised on its own: ``norm='minmax_255'`` between its minimum and maximum (the reference's vis_disparity),
+        ``'min_p95_256'`` between its minimum and its 95th percentile (viz_depth_tensor); ``inverse``: of ``1 / x``.
+        ``return_stats``: also ``[B, 2]`` fp32 ``(vmin, vmax)``.  Enqueued on the current stream: no synchronisation, no copy."""
+        if norm not in self.NORMS:
+            raise ValueError(f'scalar_to_rgb: norm must be one of {sorted(self.NORMS)}, got {norm!r}')
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3):
+            raise ValueError(f'scalar_to_rgb: expected a CUDA float32 [B, H, W] tensor, got {tuple(x.shape)} {x.dtype} {x.device}')
+        if not (lut.is_cuda and lut.device == x.device and lut.dtype == torch.uint8 and tuple(lut.shape) == (256, 3) and lut.is_contiguous()):
+            raise ValueError(f'scalar_to_rgb: expected a contiguous uint8 [256, 3] table on {x.device}, got {tuple(lut.shape)} {lut.dtype} '
+                             f'{lut.device}')
+        x = x.contiguous()
+        b, h, w = x.shape
+        rgb = torch.empty((b, h, w, 3), dtype=torch.uint8, device=x.device)
+        stats = torch.empty((b, 2), dtype=torch.float32, device=x.device) if return_stats else None
+        ws = self._ws(self.lib.um_scalar_to_rgb_workspace_bytes(b, h, w), x.device)
+        code = self._launch('scalar_to_rgb', lambda: self.lib.um_scalar_to_rgb(
+            _ptr(x), _ptr(rgb), b, h, w, int(bool(inverse)), self.NORMS[norm], _ptr(lut), _ptr(stats) if return_stats else None,
+            _ptr(ws), ws.numel(), _stream()))
+        _abi.check(code, 'um_scalar_to_rgb')
+        return (rgb, stats) if return_stats else rgb
 
     # ------------------------------------------------------------------ evaluation metrics
     @staticmethod

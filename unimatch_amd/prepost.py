@@ -9,6 +9,11 @@ the forward, crop or resize the prediction back, rescale it.
   geometry.prepare(*images, normalize=False)              images -> the model's input ``[B, 3, hp, wp]`` fp32
   geometry.restore(pred, kind='flow'|'disparity'|'depth') the prediction back at the images' size
 
+Both take ``hflip=True``: a horizontal mirror as their LAST step, which is where the reference's stereo inference puts it (resize, then
+``hflip``; resize back and rescale, then ``hflip``: evaluate_stereo.py:790-841), and ``out=``, a preallocated tensor to write into, so
+that the doubled batch of a bidirectional prediction is built without a concatenation.  The mirror is part of the one launch and
+equals ``torch.flip(<unflipped result>, [-1])`` bit for bit: the bilinear arithmetic is the mirrored column's.
+
 CUDA tensors go to the HIP kernels (``um_image_prepare``, ``um_pred_restore``: one launch each, no synchronisation); a uint8
 ``[B, H, W, 3]`` batch, as a decoder delivers frames, is accepted as it is, so 3 bytes per pixel cross the bus instead of 12.  Host
 tensors go to the restatement below, which is written out in the kernels' operation order -- ATen's bilinear arithmetic in fp32,
@@ -80,7 +85,12 @@ def resize_host(x, size):
     return ly0[:, None] * top + ly1[:, None] * bot
 
 
-def prepare_host(image, geom, mean=None, std=None):
+def prepare_host(image, geom, mean=None, std=None, hflip=False):
+    out = _prepare_host(image, geom, mean, std)
+    return out.flip(-1).contiguous() if hflip else out
+
+
+def _prepare_host(image, geom, mean=None, std=None):
     x = image.permute(0, 3, 1, 2).float() if image.dtype == torch.uint8 else image.float()
     if geom.transpose:
         x = x.transpose(-2, -1)
@@ -98,7 +108,12 @@ def prepare_host(image, geom, mean=None, std=None):
     return x.index_select(-2, iy).index_select(-1, ix).contiguous()
 
 
-def restore_host(pred, geom, kind):
+def restore_host(pred, geom, kind, hflip=False):
+    out = _restore_host(pred, geom, kind)
+    return out.flip(-1).contiguous() if hflip else out
+
+
+def _restore_host(pred, geom, kind):
     ih, iw = geom.image_size
     hp, wp = geom.size
     if geom.mode == 'pad':
@@ -187,34 +202,49 @@ class InferenceGeometry:
         return self.mode == 'pad' and self.size == self.image_size and not self.transpose
 
     # -------------------------------------------------------------- images -> model input
-    def prepare(self, *images, normalize=False):
+    def prepare(self, *images, normalize=False, hflip=False, out=None):
         """Each of ``images`` (fp32 ``[B, 3, H, W]`` or uint8 ``[B, H, W, 3]``) as the model's input ``[B, 3, hp, wp]`` fp32, in a
         list.  ``normalize``: ``False`` (flow: the model normalises raw 0..255 values itself), ``True`` (``(x / 255 - mean) / std``
         with the ImageNet constants, what the stereo and depth loaders do on the host) or ``(mean, std)``.  An fp32 batch that
-        needs nothing is returned as it is."""
+        needs nothing is returned as it is.  ``hflip``: mirrored horizontally after everything else.  ``out``: a preallocated
+        contiguous fp32 ``[B, 3, hp, wp]`` tensor per image (one tensor for one image, else a sequence; a batch slice of a larger
+        tensor qualifies) that receives the result and is returned in its place."""
         mean, std = _norm_constants(normalize)
+        if out is None:
+            dsts = [None] * len(images)
+        else:
+            dsts = [out] if torch.is_tensor(out) else list(out)
+            if len(dsts) != len(images):
+                raise ValueError(f'out: {len(dsts)} tensors for {len(images)} images')
         out = []
-        for image in images:
+        for image, dst in zip(images, dsts):
             if image_size(image) != self.shape:
                 raise ValueError(f'this geometry is for images of {self.shape[0]}x{self.shape[1]}, got {tuple(image.shape)} {image.dtype}')
             if image.dtype != torch.uint8 and not image.is_floating_point():
                 raise ValueError(f'expected float or uint8 images, got {image.dtype}')
-            if self.identity and mean is None and image.dtype == torch.float32:
+            if dst is not None and (tuple(dst.shape) != (image.shape[0], 3) + self.size or dst.dtype != torch.float32
+                                    or dst.device != image.device or not dst.is_contiguous()):
+                raise ValueError(f'out must be a contiguous float32 {(image.shape[0], 3) + self.size} tensor on {image.device}, got '
+                                 f'{tuple(dst.shape)} {dst.dtype} {dst.device}')
+            if self.identity and mean is None and image.dtype == torch.float32 and not hflip and dst is None:
                 out.append(image)
             elif image.is_cuda:
                 with torch.cuda.device(image.device):
                     src = image if image.dtype == torch.uint8 else image.float()
-                    out.append(_hip().image_prepare(src, self.size, self.mode, self.crop, self.transpose, mean, std))
+                    out.append(_hip().image_prepare(src, self.size, self.mode, self.crop, self.transpose, mean, std, hflip=hflip, out=dst))
             else:
-                out.append(prepare_host(image, self, mean, std))
+                res = prepare_host(image, self, mean, std, hflip)
+                out.append(res if dst is None else dst.copy_(res))
         return out
 
     # -------------------------------------------------------------- prediction -> the images' frame
-    def restore(self, pred, kind='flow'):
+    def restore(self, pred, kind='flow', hflip=False, out=None):
         """The prediction ``[B, C, hp, wp]`` (or ``[B, hp, wp]``, as the model returns disparities and depths) at the images' size:
         cropped, or resized and rescaled -- flow ``u * W / wp`` and ``v * H / hp``, disparity ``* W / wp``, depth not at all
         (evaluate_depth.py:131) -- and transposed back.  The reference does not swap the flow channels when it transposes back
-        (evaluate_flow.py:757-758) and neither does this: channel 0 stays the displacement along the transposed frame's x."""
+        (evaluate_flow.py:757-758) and neither does this: channel 0 stays the displacement along the transposed frame's x.
+        ``hflip``: mirrored horizontally after everything else.  ``out``: a preallocated contiguous fp32 tensor of the result's shape
+        that receives it."""
         if kind not in KINDS:
             raise ValueError(f'kind must be one of {KINDS}, got {kind!r}')
         squeeze = pred.dim() == 3
@@ -223,14 +253,21 @@ class InferenceGeometry:
         if p.dim() != 4 or p.shape[1] != channels or tuple(p.shape[-2:]) != self.size:
             raise ValueError(f'expected a {kind} prediction [B, {channels}, {self.size[0]}, {self.size[1]}]'
                              f"{' or [B, hp, wp]' if channels == 1 else ''}, got {tuple(pred.shape)}")
-        if self.identity:
+        if self.identity and not hflip and out is None:
             return pred
+        want = tuple(pred.shape[:-2]) + self.shape
+        if out is not None and (tuple(out.shape) != want or out.dtype != torch.float32 or out.device != pred.device
+                                or not out.is_contiguous()):
+            raise ValueError(f'out must be a contiguous float32 {want} tensor on {pred.device}, got {tuple(out.shape)} {out.dtype} '
+                             f'{out.device}')
+        dst = out.unsqueeze(1) if (out is not None and squeeze) else out
         if p.is_cuda:
             with torch.cuda.device(p.device):
-                out = _hip().pred_restore(p.float(), self.shape, self.mode, self.crop, kind, self.transpose)
+                res = _hip().pred_restore(p.float(), self.shape, self.mode, self.crop, kind, self.transpose, hflip=hflip, out=dst)
         else:
-            out = restore_host(p.float(), self, kind)
-        return out.squeeze(1) if squeeze else out
+            res = restore_host(p.float(), self, kind, hflip)
+            res = res if dst is None else dst.copy_(res)
+        return res.squeeze(1) if squeeze else res
 
     def scaled_intrinsics(self, intrinsics):
         """Opt-in, for depth resizes: ``intrinsics [..., 3, 3]`` with rows 0 and 1 multiplied by ``(wp - 1) / (W - 1)`` and ``(hp -
