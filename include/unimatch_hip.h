@@ -682,10 +682,18 @@ int um_scalar_to_rgb(const float* x, unsigned char* rgb, int batch, int h, int w
  *                       torch.inverse does: its inverse is all NaN, so that sample's predictions are NaN (other samples untouched).
  *                       Intrinsics / poses held in double by the caller are rounded to fp32 before the call.
  *   um_rigid_flow       flow[B,2,h,w] induced by inv_depth [B,1,h,w] and cam [B][30]: unimatch/geometry.py:99-195 as called
- *                       from the depth refinement (unimatch.py:295-305) */
+ *                       from the depth refinement (unimatch.py:295-305)
+ *   um_relative_pose_pairs  rel[T-1,4,4]: rel[t] = inv(poses[t+1]) @ poses[t] from T >= 2 absolute camera-to-world poses [T,4,4]
+ *                       (row major), the relative pose evaluate_depth.py:347-350 forms per pair on the host; the input of
+ *                       um_depth_cam_pack for the consecutive pairs of a posed video.  A pose is taken as affine, [A t; 0 0 0 1]
+ *                       (its bottom row is not read): inv = [A^-1, -A^-1 t] with the adjugate inverse of um_depth_cam_pack, the
+ *                       product formed in fp64 and each of the 12 upper entries rounded to fp32 once; the bottom row is written
+ *                       as exactly 0 0 0 1.  One thread per pair, no LU, no synchronisation.  A SINGULAR A in poses[t+1] makes
+ *                       the upper three rows of rel[t] all NaN and touches no other pair.  A null pointer or frames < 2: -1. */
 int um_flow_upsample2x(const float* flow, float* out, int batch, int channels, int h, int w, float mult, void* stream);
 int um_depth_cam_pack(const float* intrinsics, const float* pose, float* cam, int batch, float stride_div, int bidir, void* stream);
 int um_rigid_flow(const float* inv_depth, const float* cam, float* flow, int batch, int h, int w, void* stream);
+int um_relative_pose_pairs(const float* poses, float* rel, int frames, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Encoder helper (outside the hot path of SURVEY.md section 8; added because the element-wise tail of the CNN encoder

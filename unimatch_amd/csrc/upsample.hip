@@ -222,22 +222,23 @@ extern "C" int um_flow_upsample2x(const float* flow, float* out, int batch, int 
 // given in double are rounded to fp32 by the caller first, as the reference's fp32 tensors are).  A singular matrix cannot raise
 // from a kernel the way torch.inverse does (that would need the device synchronisation this kernel exists to avoid): the
 // inverse is all NaN, so every prediction of that sample is NaN and no other sample is touched (tested).
-__device__ __forceinline__ void inv3(const float* mf, float* o) {
+template <typename T>
+__device__ __forceinline__ void inv3(const float* mf, T* o) {      // T = double: the unrounded inverse, for a caller that goes on in fp64
     double m[9];
 #pragma unroll
     for (int j = 0; j < 9; ++j) m[j] = (double)mf[j];
     const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
     const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
     const double id = det != 0.0 ? 1.0 / det : (double)__builtin_nanf("");
-    o[0] = (float)(c00 * id);
-    o[1] = (float)((m[2] * m[7] - m[1] * m[8]) * id);
-    o[2] = (float)((m[1] * m[5] - m[2] * m[4]) * id);
-    o[3] = (float)(c01 * id);
-    o[4] = (float)((m[0] * m[8] - m[2] * m[6]) * id);
-    o[5] = (float)((m[2] * m[3] - m[0] * m[5]) * id);
-    o[6] = (float)(c02 * id);
-    o[7] = (float)((m[1] * m[6] - m[0] * m[7]) * id);
-    o[8] = (float)((m[0] * m[4] - m[1] * m[3]) * id);
+    o[0] = (T)(c00 * id);
+    o[1] = (T)((m[2] * m[7] - m[1] * m[8]) * id);
+    o[2] = (T)((m[1] * m[5] - m[2] * m[4]) * id);
+    o[3] = (T)(c01 * id);
+    o[4] = (T)((m[0] * m[8] - m[2] * m[6]) * id);
+    o[5] = (T)((m[2] * m[3] - m[0] * m[5]) * id);
+    o[6] = (T)(c02 * id);
+    o[7] = (T)((m[1] * m[6] - m[0] * m[7]) * id);
+    o[8] = (T)((m[0] * m[4] - m[1] * m[3]) * id);
 }
 
 __global__ void depth_cam_pack_kernel(const float* __restrict__ intr, const float* __restrict__ pose, float* __restrict__ cam, int batch,
@@ -280,6 +281,45 @@ extern "C" int um_depth_cam_pack(const float* intrinsics, const float* pose, flo
     }
     const int n = bidir ? 2 * batch : batch;
     hipLaunchKernelGGL(depth_cam_pack_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, intrinsics, pose, cam, batch, stride_div, bidir);
+    return (int)hipGetLastError();
+}
+
+// relative_pose_pairs: rel[t] = inv(poses[t+1]) @ poses[t] for the T - 1 consecutive pairs of T absolute camera-to-world poses
+// (evaluate_depth.py:347-350 per pair, on the host there).  One thread per pair.  A pose is affine, so with poses[t+1] = [A b] and
+// poses[t] = [C d]: rel = [A^-1 C, A^-1 (d - b)] -- A^-1 from inv3 (fp64 adjugate, kept in fp64 here), the products accumulated
+// in fp64 and each of the 12 upper entries rounded to fp32 once; the bottom row is written as 0 0 0 1.
+// A singular A: inv3 gives all NaN, so the upper three rows of that pair are NaN (the products below are sums that each contain a
+// NaN term) and no other pair is touched -- the convention of depth_cam_pack.
+__global__ void relative_pose_pairs_kernel(const float* __restrict__ poses, float* __restrict__ rel, int pairs) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= pairs) return;
+    const float* p = poses + (long)t * 16;          // reference view
+    const float* q = p + 16;                        // target view: inverted
+    const float a[9] = {q[0], q[1], q[2], q[4], q[5], q[6], q[8], q[9], q[10]};
+    double ai[9];
+    inv3(a, ai);
+    const double d[3] = {(double)p[3] - (double)q[3], (double)p[7] - (double)q[7], (double)p[11] - (double)q[11]};
+    float* o = rel + (long)t * 16;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double i0 = ai[3 * r], i1 = ai[3 * r + 1], i2 = ai[3 * r + 2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[4 * r + c] = (float)(i0 * (double)p[c] + i1 * (double)p[4 + c] + i2 * (double)p[8 + c]);
+        o[4 * r + 3] = (float)(i0 * d[0] + i1 * d[1] + i2 * d[2]);
+    }
+    o[12] = 0.f;
+    o[13] = 0.f;
+    o[14] = 0.f;
+    o[15] = 1.f;
+}
+
+extern "C" int um_relative_pose_pairs(const float* poses, float* rel, int frames, void* stream) {
+    if (!poses || !rel || frames < 2) {
+        um_set_error("um_relative_pose_pairs: null pointer or fewer than two frames");
+        return -1;
+    }
+    const int pairs = frames - 1;
+    hipLaunchKernelGGL(relative_pose_pairs_kernel, dim3((pairs + 63) / 64), dim3(64), 0, (hipStream_t)stream, poses, rel, pairs);
     return (int)hipGetLastError();
 }
 

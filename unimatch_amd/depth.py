@@ -8,6 +8,11 @@ reference's ``viz_depth_tensor(1 / depth)`` colouring (:mod:`unimatch_amd.visual
 searches the inverse depths ``1 / max_depth .. 1 / min_depth``.  Frames are uploaded as uint8 and normalised on the device; like the
 reference's runner this one RESIZES (to the next multiple of ``padding_factor`` or to ``inference_size``) and does NOT rescale the
 intrinsics; ``--scale-intrinsics`` opts into :meth:`InferenceGeometry.scaled_intrinsics`.  Reading frames needs PIL.
+
+``--pairs-per-launch N`` runs the scene through :meth:`UniMatch.forward_sequence` (``task='depth'``) instead: every frame is read,
+uploaded, prepared and encoded once, the absolute poses are uploaded once and the relative poses are formed on the device, N pairs go
+through the match step per launch, and the coloured images come back once per piece of N pairs.  The files written are those of the
+default mode; all frames must have one size.
 """
 import argparse
 import glob
@@ -41,14 +46,21 @@ def relative_pose(pose_ref, pose_tgt):
 
 
 def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_size=None, min_depth=0.5, max_depth=10.,
-              num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, scale_intrinsics=False, device='cuda'):
-    """``inference_depth`` over the scene: returns the number of frames written (one less than the scene has)."""
+              num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, scale_intrinsics=False, device='cuda',
+              pairs_per_launch=None):
+    """``inference_depth`` over the scene: returns the number of frames written (one less than the scene has).
+    ``pairs_per_launch=N``: sequence mode (the module docstring), in pieces of N pairs; ``None``: one ``predict`` per pair."""
     from .io import write_png8
     from .prepost import InferenceGeometry
     imgs, poses, k = read_scene(scene_dir)
     os.makedirs(out_dir, exist_ok=True)
-    skip = ('task', 'min_depth', 'max_depth', 'num_depth_candidates', 'depth_from_argmax', 'pred_bidir_depth', 'intrinsics', 'pose')
+    skip = ('task', 'min_depth', 'max_depth', 'num_depth_candidates', 'depth_from_argmax', 'pred_bidir_depth', 'intrinsics', 'pose',
+            'poses')
     fwd_kw = {key: v for key, v in fwd_kw.items() if key not in skip}
+    if pairs_per_launch is not None:
+        return _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, inference_size, min_depth, max_depth,
+                                   num_depth_candidates, depth_from_argmax, pred_bidir_depth, scale_intrinsics, device,
+                                   int(pairs_per_launch))
     for i in range(len(imgs) - 1):
         ref, tgt = read_frame_u8(imgs[i])[None].to(device), read_frame_u8(imgs[i + 1])[None].to(device)
         size = tuple(inference_size) if inference_size else nearest_size(ref.shape[1:3], padding_factor)
@@ -68,6 +80,53 @@ def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_si
     return max(0, len(imgs) - 1)
 
 
+def _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, inference_size, min_depth, max_depth,
+                        num_depth_candidates, depth_from_argmax, pred_bidir_depth, scale_intrinsics, device, step):
+    """The scene through ``forward_sequence(task='depth')`` in pieces of ``step`` pairs (``step + 1`` frames first, then ``step`` frames
+    joined by the carry), so that at most ``step + 1`` frames and their predictions are resident."""
+    from .io import write_png8
+    from .prepost import InferenceGeometry
+    if step < 1:
+        raise ValueError('pairs_per_launch must be >= 1')
+    if len(imgs) < 2:
+        return 0
+    geom = intrinsics = carry = shape = None
+    pose_dev = torch.from_numpy(poses).to(device)                                            # absolute, uploaded once
+    lo = 0
+    while lo < len(imgs):
+        hi = min(len(imgs), lo + step + (1 if carry is None else 0))
+        host = [read_frame_u8(f) for f in imgs[lo:hi]]
+        for f, frame in zip(imgs[lo:hi], host):
+            shape = shape or tuple(frame.shape)
+            if tuple(frame.shape) != shape:
+                raise ValueError(f'{f} is {tuple(frame.shape[:2])}, the scene began with {shape[:2]}: --pairs-per-launch needs frames '
+                                 'of one size')
+        if geom is None:
+            size = tuple(inference_size) if inference_size else nearest_size(shape[:2], padding_factor)
+            geom = InferenceGeometry.resized(shape[:2], size)
+            intrinsics = torch.from_numpy(k)[None].to(device)
+            if scale_intrinsics:
+                intrinsics = geom.scaled_intrinsics(intrinsics)
+        frames, = geom.prepare(torch.stack(host, 0).to(device), normalize=True)               # uint8 up, normalised on the device
+        with torch.no_grad():
+            out = model.forward_sequence(frames, task='depth', intrinsics=intrinsics, poses=pose_dev[lo:hi], carry=carry,
+                                         pairs_per_launch=step, min_depth=1. / max_depth, max_depth=1. / min_depth,
+                                         num_depth_candidates=num_depth_candidates, depth_from_argmax=depth_from_argmax,
+                                         pred_bidir_depth=pred_bidir_depth, **fwd_kw)
+        carry = out['carry']
+        first = lo - (0 if lo == 0 else 1)                                                   # the frame of the piece's first pair
+        depth = [out['depth']] + ([out['depth_bwd']] if pred_bidir_depth else [])
+        n = depth[0].shape[0]
+        rgb = inverse_depth_to_image(geom.restore(torch.cat(depth, 0), 'depth')).cpu().numpy()   # one copy back per piece
+        for j in range(n):
+            stem = os.path.join(out_dir, os.path.splitext(os.path.basename(imgs[first + j]))[0])
+            write_png8(stem + '.png', rgb[j])
+            if pred_bidir_depth:
+                write_png8(stem + '_bwd.png', rgb[n + j])
+        lo = hi
+    return len(imgs) - 1
+
+
 def main(argv=None):
     from .synth import CONFIGS
     ap = argparse.ArgumentParser(description='depth of a posed ScanNet-layout scene (UniMatch.predict), coloured on the device')
@@ -81,6 +140,8 @@ def main(argv=None):
     ap.add_argument('--depth-from-argmax', action='store_true')
     ap.add_argument('--pred-bidir-depth', action='store_true')
     ap.add_argument('--scale-intrinsics', action='store_true', help='rescale the intrinsics with the resize (the reference does not)')
+    ap.add_argument('--pairs-per-launch', type=int, default=None, metavar='N',
+                    help='sequence mode: encode every frame once and match N pairs per launch (frames of one size)')
     ap.add_argument('--model-config', default='gmdepth_s1', choices=[k for k, v in CONFIGS.items() if v[1].get('task') == 'depth'])
     ap.add_argument('--weights', default=None, help="checkpoint (the reference's: a state_dict, or {'model': state_dict}); "
                                                     'default: the seeded synthetic weights')
@@ -90,7 +151,7 @@ def main(argv=None):
     n = run_depth(model, args.scene, args.out, fwd_kw, padding_factor=args.padding_factor, inference_size=args.inference_size,
                   min_depth=args.min_depth, max_depth=args.max_depth, num_depth_candidates=args.num_depth_candidates,
                   depth_from_argmax=args.depth_from_argmax, pred_bidir_depth=args.pred_bidir_depth,
-                  scale_intrinsics=args.scale_intrinsics)
+                  scale_intrinsics=args.scale_intrinsics, pairs_per_launch=args.pairs_per_launch)
     print(f'{n} frames written to {args.out}')
 
 

@@ -617,7 +617,8 @@ class UniMatch(nn.Module):
 
     def forward_sequence(self, frames, attn_type=None, attn_splits_list=None, corr_radius_list=None, prop_radius_list=None,
                          num_reg_refine=1, pred_bidir_flow=False, consistency_check=False, colorize=False, pairs_per_launch=8,
-                         carry=None, task='flow'):
+                         carry=None, task='flow', intrinsics=None, poses=None, min_depth=1. / 0.5, max_depth=1. / 10,
+                         num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False):
         """Optical flow of every pair (t, t+1) of a frame sequence ``frames [T, 3, H, W]`` (raw 0..255), each frame encoded ONCE.
 
         The reference's ``inference_flow`` (evaluate_flow.py:640-831) runs the model on each pair, so every interior frame goes through
@@ -630,11 +631,30 @@ class UniMatch(nn.Module):
         Returns ``{'flow': [P, 2, H, W], 'carry': ...}`` with ``P = T - 1`` (``T`` with a carry), plus ``'flow_bwd'`` with
         ``pred_bidir_flow``, ``'occ_fwd'`` / ``'occ_bwd'`` ``[P, H, W]`` float with ``consistency_check`` (the reference's
         forward_backward_consistency_check) and ``'flow_rgb'`` (``'flow_bwd_rgb'``) ``[P, H, W, 3]`` uint8 with ``colorize`` (its
-        flow_to_image, each image normalised by its own maximum)."""
+        flow_to_image, each image normalised by its own maximum).
+
+        ``task='depth'``: the depth of every frame t of a posed video from the pair (t, t + 1) -- the one other task whose consecutive
+        pairs share a frame (a stereo pair shares nothing with the next one: ``task='stereo'`` raises).  ``frames`` are what
+        :meth:`forward` takes for depth (normalised already), ``poses [T, 4, 4]`` the frames' absolute camera-to-world matrices and
+        ``intrinsics`` ``[1, 3, 3]`` (one camera) or ``[T, 3, 3]`` (pair t uses row t for both views, as the reference does with the
+        first image's).  The relative poses ``inv(poses[t + 1]) @ poses[t]`` of the whole call come from one launch
+        (``HipOps.relative_pose_pairs``; fp32 ``torch.linalg.inv`` for CPU tensors) and each chunk's rows go into the match step
+        of :meth:`forward` unchanged; ``min_depth`` ... ``pred_bidir_depth`` mean what they mean there.  The carry also holds the last
+        frame's pose and intrinsics row.  Returns ``{'depth': [P, H, W], 'carry': ...}``, plus ``'depth_bwd'`` (the depth of frame t + 1
+        seen from pair t) with ``pred_bidir_depth`` and ``'depth_rgb'`` (``'depth_bwd_rgb'``) ``[P, H, W, 3]`` uint8 with ``colorize``
+        (``visualize.inverse_depth_to_image``).  On the GPU a depth call never waits for the device.  The depth keywords are ignored
+        for ``task='flow'``."""
         if self.training:
             raise RuntimeError('this module implements inference only: call .eval()')
-        if task != 'flow':
-            raise NotImplementedError('forward_sequence is optical flow only')
+        if task == 'stereo':
+            raise NotImplementedError("forward_sequence: consecutive stereo pairs share no frame, so there is nothing to encode once; "
+                                      "batch the pairs through forward() / predict()")
+        if task not in ('flow', 'depth'):
+            raise ValueError(f"task must be 'flow' or 'depth', got {task!r}")
+        if task == 'depth':
+            return self._depth_sequence(frames, attn_type, attn_splits_list, prop_radius_list, num_reg_refine, pred_bidir_flow,
+                                        consistency_check, colorize, pairs_per_launch, carry, intrinsics, poses, min_depth, max_depth,
+                                        num_depth_candidates, depth_from_argmax, pred_bidir_depth)
         if consistency_check and not pred_bidir_flow:
             raise AssertionError('consistency_check needs pred_bidir_flow=True (as the reference asserts)')
         if frames.dim() != 4 or frames.shape[1] != 3:
@@ -643,6 +663,8 @@ class UniMatch(nn.Module):
             raise ValueError('pairs_per_launch must be >= 1')
         if carry is not None and tuple(carry['frame'].shape[1:]) != tuple(frames.shape[1:]):
             raise ValueError(f'carry holds a {tuple(carry["frame"].shape[2:])} frame, frames are {tuple(frames.shape[2:])}')
+        if carry is not None and 'pose' in carry:
+            raise ValueError("carry comes from a task='depth' sequence (its features are those of normalised frames)")
         pairs = frames.shape[0] - (0 if carry is not None else 1)
         if pairs < 1:
             raise ValueError('no frame pair: give at least two frames, or one with a carry')
@@ -697,10 +719,95 @@ class UniMatch(nn.Module):
             result['carry'] = {'features': [p.clone() for p in prev], 'frame': last.clone(), 'state': self._carry_state(frames)}
         return result
 
-    def _match_pairs(self, chunk, nb, kw):
-        """The match step of the ``nb`` pairs of consecutive frames whose features are ``chunk[s]`` (per scale, a list of pieces
-        ``[N_i, C, h, w]`` that together hold the ``nb + 1`` frames in order) -> predictions ``[bidir * nb, 2, H, W]`` in the reference's
-        [forward; backward] order.  The stream ``[F[lo:hi]; F[lo+1:hi+1]]`` of pairs lo .. hi-1 is ONE concatenation per scale.  Where
+    def _depth_sequence(self, frames, attn_type, attn_splits_list, prop_radius_list, num_reg_refine, pred_bidir_flow, consistency_check,
+                        colorize, pairs_per_launch, carry, intrinsics, poses, min_depth, max_depth, num_depth_candidates,
+                        depth_from_argmax, pred_bidir_depth):
+        """:meth:`forward_sequence` for ``task='depth'`` (documented there).  Frame j of the call -- the carried frame first, when
+        there is a carry -- has pose ``pose_all[j]`` and intrinsics ``k_all[j]``; pair j is frames (j, j + 1)."""
+        # what forward (_forward_one) asserts for depth
+        assert not pred_bidir_flow, 'pred_bidir_flow is a flow option'
+        assert not consistency_check, 'consistency_check is a flow option (it needs pred_bidir_flow)'
+        assert self.num_scales == 1
+        assert len(attn_splits_list) == len(prop_radius_list) == self.num_scales == 1
+        if frames.dim() != 4 or frames.shape[1] != 3:
+            raise ValueError(f'frames: expected [T, 3, H, W], got {tuple(frames.shape)}')
+        if int(pairs_per_launch) < 1:
+            raise ValueError('pairs_per_launch must be >= 1')
+        if poses is None or intrinsics is None:
+            raise ValueError("task='depth' needs poses [T, 4, 4] (absolute camera-to-world) and intrinsics [1, 3, 3] or [T, 3, 3]")
+        count = frames.shape[0]
+        if poses.dim() != 3 or tuple(poses.shape) != (count, 4, 4):
+            raise ValueError(f'poses: expected [{count}, 4, 4] (one per frame), got {tuple(poses.shape)}')
+        if intrinsics.dim() != 3 or tuple(intrinsics.shape[1:]) != (3, 3) or intrinsics.shape[0] not in (1, count):
+            raise ValueError(f'intrinsics: expected [1, 3, 3] or [{count}, 3, 3], got {tuple(intrinsics.shape)}')
+        if carry is not None:
+            if 'pose' not in carry:
+                raise ValueError("carry comes from a task='flow' sequence: it holds no pose")
+            if tuple(carry['frame'].shape[1:]) != tuple(frames.shape[1:]):
+                raise ValueError(f'carry holds a {tuple(carry["frame"].shape[2:])} frame, frames are {tuple(frames.shape[2:])}')
+        if count - (0 if carry is not None else 1) < 1:
+            raise ValueError('no frame pair: give at least two frames, or one with a carry')
+        kw = dict(attn_type=attn_type if attn_type is not None else '', attn_splits_list=attn_splits_list, corr_radius_list=None,
+                  prop_radius_list=prop_radius_list, num_reg_refine=num_reg_refine, pred_bidir_flow=False, task='depth',
+                  min_depth=min_depth, max_depth=max_depth, num_depth_candidates=num_depth_candidates,
+                  depth_from_argmax=depth_from_argmax, pred_bidir_depth=pred_bidir_depth)
+        import contextlib
+        from . import visualize
+        dev = frames.device
+        ops = self.ops
+        if self.check_weights:
+            self._check_weight_print()
+        if frames.is_cuda and self.check_range and getattr(ops, 'mode', 1) == 0:
+            from . import _abi
+            _abi.check_operand_range('an earlier forward of this process: ')
+        guard = torch.cuda.device(dev) if frames.is_cuda else contextlib.nullcontext()
+        step = int(pairs_per_launch)
+        out = {k: [] for k in ('depth', 'depth_bwd', 'depth_rgb', 'depth_bwd_rgb')}
+        with guard, torch.no_grad():
+            pose_all = poses.to(dev).float()
+            k_all = intrinsics.to(dev).float().expand(count, 3, 3)
+            prev = None
+            if carry is not None:
+                pose_all = torch.cat([carry['pose'].to(dev), pose_all], 0)
+                k_all = torch.cat([carry['intrinsics'].to(dev), k_all], 0)
+                if self._carry_valid(carry, frames):
+                    prev = carry['features']
+                else:                                     # stale: the stored frame is encoded with the first chunk
+                    frames = torch.cat([carry['frame'].to(dev), frames], 0)
+            if hasattr(ops, 'relative_pose_pairs') and pose_all.is_cuda:   # every pair of the call in one launch, no sync
+                rel = ops.relative_pose_pairs(pose_all)
+            else:
+                rel = torch.linalg.inv(pose_all[1:]) @ pose_all[:-1]
+            i, done = 0, 0                                # first new frame / first pair of the next chunk
+            while i < frames.shape[0] - (1 if prev is None else 0):
+                new = frames[i:i + step + (1 if prev is None else 0)]
+                feats = self._encode((new,), 'depth')
+                chunk = [([] if prev is None else [p]) + [f] for p, f in zip(prev or feats, feats)]
+                nb = new.shape[0] - (1 if prev is None else 0)
+                i += new.shape[0]
+                pred = self._match_pairs(chunk, nb, kw, k_all[done:done + nb], rel[done:done + nb])
+                done += nb
+                prev = [f[f.shape[0] - 1:] for f in feats]
+                fwd = pred[:nb]
+                out['depth'].append(fwd)
+                if pred_bidir_depth:
+                    bwd = pred[nb:]
+                    out['depth_bwd'].append(bwd)
+                if colorize:
+                    out['depth_rgb'].append(visualize.inverse_depth_to_image(fwd))
+                    if pred_bidir_depth:
+                        out['depth_bwd_rgb'].append(visualize.inverse_depth_to_image(bwd))
+            last = frames[frames.shape[0] - 1:]
+            result = {k: v[0] if len(v) == 1 else torch.cat(v, 0) for k, v in out.items() if v}
+            result['carry'] = {'features': [p.clone() for p in prev], 'frame': last.clone(), 'state': self._carry_state(frames),
+                               'pose': pose_all[-1:].clone(), 'intrinsics': k_all[-1:].clone()}
+        return result
+
+    def _match_pairs(self, chunk, nb, kw, intrinsics=None, pose=None):
+        """The match step (task ``kw['task']``) of the ``nb`` pairs of consecutive frames whose features are ``chunk[s]`` (per scale, a
+        list of pieces ``[N_i, C, h, w]`` that together hold the ``nb + 1`` frames in order) -> predictions ``[bidir * nb, ...]`` in the
+        reference's [forward; backward] order.  The stream ``[F[lo:hi]; F[lo+1:hi+1]]`` of pairs lo .. hi-1 is ONE concatenation per
+        scale.  ``intrinsics [nb, 3, 3]``, ``pose [nb, 4, 4]`` (depth): per pair, sliced with the features.  Where
         ``streams.forward_parts`` says so, the pairs run as concurrent parts on the process-wide side streams (``streams.PartRunner``)."""
         def frames_of(pieces, a, b):                  # the pieces that hold frames a .. b-1 of the chunk
             out, base = [], 0
@@ -714,21 +821,24 @@ class UniMatch(nn.Module):
         def stream(lo, hi):
             return [torch.cat(frames_of(pieces, lo, hi) + frames_of(pieces, lo + 1, hi + 1), 0) for pieces in chunk]
 
+        def rows(t, lo, hi):
+            return None if t is None else t[lo:hi]
+
         ref = chunk[-1][-1]
         h8, w8 = ref.shape[-2:]
-        parts = self._plan_parts(self.launch_parts, 'flow', kw['attn_type'], nb, self.upsample_factor * h8, self.upsample_factor * w8,
+        parts = self._plan_parts(self.launch_parts, kw['task'], kw['attn_type'], nb, self.upsample_factor * h8, self.upsample_factor * w8,
                                  ref.is_cuda)
         if parts <= 1:
-            return self._match(stream(0, nb), nb, **kw)['flow_preds'][0]
+            return self._match(stream(0, nb), nb, intrinsics=intrinsics, pose=pose, **kw)['flow_preds'][0]
 
         def prepare(r):
             lo, hi = shard_bounds(nb, r, parts)
-            return stream(lo, hi), hi - lo
+            return stream(lo, hi), hi - lo, rows(intrinsics, lo, hi), rows(pose, lo, hi)
 
         def compute(r, ins):
-            return self._match(ins[0], ins[1], **kw)['flow_preds']
+            return self._match(ins[0], ins[1], intrinsics=ins[2], pose=ins[3], **kw)['flow_preds']
 
-        bidir = 2 if kw['pred_bidir_flow'] else 1
+        bidir = 2 if (kw['pred_bidir_flow'] or kw.get('pred_bidir_depth')) else 1
         return self._runner.run_parts(self, parts, nb, bidir, (nb,) + tuple(ref.shape[1:]), ref.device, kw, prepare,
                                       compute)['flow_preds'][0]
 

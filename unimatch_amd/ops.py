@@ -721,6 +721,16 @@ class HipOps(WorkspaceRegistry):
         _abi.check(self.lib.um_rigid_flow(_ptr(inv_depth), _ptr(cam), _ptr(out), b, h, w, _stream()), 'um_rigid_flow')
         return out
 
+    def relative_pose_pairs(self, poses):
+        """``[T-1, 4, 4]``: ``inv(poses[t+1]) @ poses[t]`` of the consecutive pairs of ``poses [T, 4, 4]`` (absolute camera-to-world,
+        ``T >= 2``) on the current stream, no synchronisation (``um_relative_pose_pairs``)."""
+        if not (poses.dim() == 3 and tuple(poses.shape[1:]) == (4, 4) and poses.shape[0] >= 2 and poses.is_cuda):
+            raise ValueError('relative_pose_pairs: expected CUDA poses [T,4,4] with T >= 2')
+        p = poses.float().contiguous()
+        rel = torch.empty((p.shape[0] - 1, 4, 4), dtype=torch.float32, device=p.device)
+        _abi.check(self.lib.um_relative_pose_pairs(_ptr(p), _ptr(rel), p.shape[0], _stream()), 'um_relative_pose_pairs')
+        return rel
+
     # ------------------------------------------------------------------ encoder helper (outside the hot path)
     def instance_norm(self, x, relu=True, shortcut=None, eps=1e-5):
         """Fused InstanceNorm2d(affine=False) [+ ReLU] [+ shortcut, ReLU] on a contiguous NCHW fp32 map."""
