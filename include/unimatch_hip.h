@@ -695,6 +695,53 @@ int um_depth_cam_pack(const float* intrinsics, const float* pose, float* cam, in
 int um_rigid_flow(const float* inv_depth, const float* cam, float* flow, int batch, int h, int w, void* stream);
 int um_relative_pose_pairs(const float* poses, float* rel, int frames, void* stream);
 
+/* Cross-view consistency and point clouds (csrc/geometry.hip): what a caller does with predicted disparities / depths of several
+ * views.  Memory-bound, one thread per pixel; every entry point enqueues on `stream` and never synchronises; no global atomics, no
+ * counters, nothing kept between calls; fp32 arithmetic with every product, sum, quotient and square root rounded on its own.
+ * batch * h * w < 2^31.  A null pointer (where not stated as optional) or a bad size returns UM_ERR_BAD_ARG and names the entry point
+ * in um_last_error_string.  Invalid values (NaN, inf, non-positive depths, a singular camera) never cause an out-of-bounds read: taps
+ * are taken from clamped addresses and discarded.
+ *   um_disp_consistency   the left / right check of a rectified pair: disp_left, disp_right [B,H,W] fp32 -> occ_left, occ_right
+ *                         [B,H,W] fp32 in {0, 1}, 1 = occluded.  It is um_fwd_bwd_occlusion on the flows fwd = (-disp_left, 0) and
+ *                         bwd = (+disp_right, 0), evaluated without the zero channel: the other view's disparity is sampled linearly
+ *                         along the row at x - dL(x) (for the right view at x + dR(x)) -- two taps, zeros outside, the same
+ *                         normalise / un-normalise round trip of the x coordinate -- and a pixel is occluded where
+ *                         |dL - dR'| > alpha (|dL| + |dR|) + beta.  As in the flow check both magnitudes of the threshold are the
+ *                         unwarped ones at the pixel itself; only the difference uses the sampled dR'.  W >= 2 (H >= 1).
+ *   um_depth_consistency  the round trip of every pixel of a reference view through a source view: depth_ref, depth_src [B,H,W] fp32
+ *                         METRIC depths (not inverse), cam_fwd, cam_inv [B][30] the Kinv | R | t | K records of um_depth_cam_pack at
+ *                         stride_div = 1 for the ref -> src pose and for its inverse (the two halves of a bidir pack) -> occ [B,H,W]
+ *                         fp32 in {0, 1} and, when not NULL, err_px, err_rel [B,H,W] fp32.  Per pixel p = (x, y) with d = depth_ref(p):
+ *                           1. (u, v) = project(R (d Kinv p) + t) of cam_fwd, the divisor clamped at 1e-3 (unimatch/geometry.py:99-154);
+ *                           2. in view iff 0 <= u <= W - 1 and 0 <= v <= H - 1;
+ *                           3. s = bilinear sample of depth_src at (u, v): taps floor and min(floor + 1, size - 1), weights
+ *                              (1 - ax)(1 - ay), ax (1 - ay), (1 - ax) ay, ax ay, summed in that order, taps of weight zero skipped;
+ *                           4. X' = R' (s Kinv (u, v, 1)) + t' of cam_inv; d' = X'_z, p' = project(X') as in step 1;
+ *                           5. err_px = |p' - p|, err_rel = |d' - d| / d;
+ *                           6. occ = 0 iff err_px < px_thr and err_rel < rel_thr.
+ *                         The pixel is occluded with both errors +inf when d is not finite or <= 0, when it is out of view, or when a
+ *                         tap of non-zero weight is not finite or <= 0.  One launch, whatever the number of directed pairs in B.
+ *   um_points_pack        a dense world-space point list of the selected pixels of depth [B,H,W] fp32: cam_world [B][30] is the cam
+ *                         record of (intrinsics, camera-to-world pose); keep [B,H,W] fp32 (NULL: all; non-zero = keep); colors
+ *                         [B,H,W,3] uint8 and rgb both NULL or both given.  Pixel (b, y, x) is selected iff x % stride == 0 and
+ *                         y % stride == 0, it is kept, and its depth is finite with min_depth < d < max_depth.  The selected pixels
+ *                         are written as xyz[n] = R (d Kinv p) + t (fp32 [N,3]) and rgb[n] = colors[b, y, x], n ascending in
+ *                         (b, y, x): a STABLE compaction, n is the pixel's rank among the selected ones (what torch.nonzero gives).
+ *                         count (one int32 ON THE DEVICE) receives N; xyz / rgb must hold a row for every candidate pixel
+ *                         (B ceil(H / stride) ceil(W / stride)).  Three launches: one count per workgroup of 256 pixels (wave-64
+ *                         ballot + popcount) into `workspace`, one workgroup's exclusive scan of the counts (which writes `count`),
+ *                         and a scatter at scanned offset + rank inside the workgroup.  Every workspace slot that is read was written
+ *                         by the same call; the order does not depend on scheduling.  workspace (4-byte aligned) >=
+ *                         um_points_workspace_bytes(batch, h, w, stride) (0 for bad sizes), else UM_ERR_WORKSPACE. */
+int um_disp_consistency(const float* disp_left, const float* disp_right, float* occ_left, float* occ_right, int batch, int h, int w,
+                        float alpha, float beta, void* stream);
+int um_depth_consistency(const float* depth_ref, const float* depth_src, const float* cam_fwd, const float* cam_inv, float* occ,
+                         float* err_px, float* err_rel, int batch, int h, int w, float px_thr, float rel_thr, void* stream);
+size_t um_points_workspace_bytes(int batch, int h, int w, int stride);
+int um_points_pack(const float* depth, const float* cam_world, const float* keep, const unsigned char* colors, float* xyz,
+                   unsigned char* rgb, int* count, int batch, int h, int w, int stride, float min_depth, float max_depth, void* workspace,
+                   size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Encoder helper (outside the hot path of SURVEY.md section 8; added because the element-wise tail of the CNN encoder
  * had become the largest non-convolution cost):  fused InstanceNorm2d(affine=False) + ReLU (+ shortcut + ReLU),

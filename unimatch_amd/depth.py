@@ -13,6 +13,21 @@ intrinsics; ``--scale-intrinsics`` opts into :meth:`InferenceGeometry.scaled_int
 uploaded, prepared and encoded once, the absolute poses are uploaded once and the relative poses are formed on the device, N pairs go
 through the match step per launch, and the coloured images come back once per piece of N pairs.  The files written are those of the
 default mode; all frames must have one size.
+
+Values and geometry (both modes write the same files):
+
+  ``--save-depth``          ``<stem>_depth.png``: the depth in millimetres as a 16-bit PNG, the format the reference's ScanNet loader
+                            divides by 1000 (rounded, 0 where the depth is not finite; 65535 mm at most)
+  ``--consistency-check``   ``<stem>_occ.png``: 255 where fewer than ``--min-views`` of the frame's neighbours (the previous and the next
+                            frame) agree with its depth to ``--px-thr`` pixels and ``--rel-thr`` relative depth, 0 where the pixel is kept
+  ``--save-ply FILE``       the fused, consistency-filtered, coloured world point cloud of the whole scene (binary PLY), every
+                            ``--ply-stride``-th pixel of every row and column (:func:`unimatch_amd.geometry.fuse_depth_sequence`)
+
+Frame i has a depth map through the pair (i, i + 1); the last frame has one only with ``--pred-bidir-depth``, through the last pair's
+backward prediction, and gets its ``_depth.png`` / ``_occ.png`` then.  The geometry always uses the depth restored to the frames' own
+size with the scene's own intrinsics, whatever ``--scale-intrinsics`` gave the model.  For ``--consistency-check`` and ``--save-ply`` the
+runner keeps the restored depth maps and the uint8 frames of the whole scene resident on the device -- 4 + 3 bytes per pixel and frame
+-- and fuses after the last piece (all frames of one size).
 """
 import argparse
 import glob
@@ -45,22 +60,76 @@ def relative_pose(pose_ref, pose_tgt):
     return (np.linalg.inv(pose_tgt.astype(np.float32)) @ pose_ref.astype(np.float32)).astype(np.float32)
 
 
+class _SceneCollector:
+    """What ``--save-depth``, ``--consistency-check`` and ``--save-ply`` need of a scene: writes each restored depth map as it
+    arrives and, for the latter two, keeps it and its uint8 frame on the device until :meth:`finish` fuses the scene."""
+
+    def __init__(self, out_dir, imgs, poses, k, save_depth, consistency_check, save_ply, ply_stride, min_views, px_thr, rel_thr):
+        self.out_dir, self.imgs, self.poses, self.k = out_dir, imgs, poses, k
+        self.save_depth, self.consistency_check, self.save_ply = save_depth, consistency_check, save_ply
+        self.ply_stride, self.min_views, self.px_thr, self.rel_thr = ply_stride, min_views, px_thr, rel_thr
+        self.fuse = bool(consistency_check or save_ply)
+        self.depths, self.frames = [], []
+
+    def stem(self, i):
+        return os.path.join(self.out_dir, os.path.splitext(os.path.basename(self.imgs[i]))[0])
+
+    def add(self, i, depth, frame_u8):
+        """Frame ``i`` (they arrive in order): its restored depth ``[H, W]`` fp32 and its frame ``[H, W, 3]`` uint8, on one device."""
+        from .io import write_png16
+        if self.save_depth:
+            mm = torch.nan_to_num(depth * 1000., nan=0., posinf=0., neginf=0.).round().clamp(0., 65535.)
+            write_png16(self.stem(i) + '_depth.png', mm.to(torch.int32).cpu().numpy().astype(np.uint16))
+        if self.fuse:
+            assert i == len(self.depths)
+            if self.depths and depth.shape != self.depths[0].shape:
+                raise ValueError(f'{self.imgs[i]} is {tuple(depth.shape)}, the scene began with {tuple(self.depths[0].shape)}: '
+                                 '--consistency-check / --save-ply need frames of one size')
+            self.depths.append(depth)
+            self.frames.append(frame_u8)
+
+    def finish(self):
+        from .geometry import fuse_depth_sequence
+        from .io import write_ply, write_png8
+        if not self.fuse:
+            return
+        n = len(self.depths)
+        if n < 2:
+            raise ValueError(f'--consistency-check / --save-ply need at least two frames with a depth map, the scene gave {n}')
+        depths, colors = torch.stack(self.depths, 0), torch.stack(self.frames, 0)
+        dev = depths.device
+        out = fuse_depth_sequence(depths, torch.from_numpy(self.k)[None].to(dev), torch.from_numpy(self.poses[:n]).to(dev), colors,
+                                  px_thr=self.px_thr, rel_thr=self.rel_thr, min_views=self.min_views, stride=self.ply_stride)
+        if self.consistency_check:
+            occ = ((1. - out['keep']) * 255.).to(torch.uint8).cpu().numpy()
+            for i in range(n):
+                write_png8(self.stem(i) + '_occ.png', occ[i])
+        if self.save_ply:
+            write_ply(self.save_ply, out['xyz'].cpu().numpy(), out['rgb'].cpu().numpy())
+
+
 def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_size=None, min_depth=0.5, max_depth=10.,
               num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, scale_intrinsics=False, device='cuda',
-              pairs_per_launch=None):
+              pairs_per_launch=None, save_depth=False, consistency_check=False, save_ply=None, ply_stride=1, min_views=1, px_thr=1.0,
+              rel_thr=0.01):
     """``inference_depth`` over the scene: returns the number of frames written (one less than the scene has).
-    ``pairs_per_launch=N``: sequence mode (the module docstring), in pieces of N pairs; ``None``: one ``predict`` per pair."""
+    ``pairs_per_launch=N``: sequence mode (the module docstring), in pieces of N pairs; ``None``: one ``predict`` per pair.
+    ``save_depth``, ``consistency_check``, ``save_ply`` (a file name): the value and geometry outputs of the module docstring."""
     from .io import write_png8
     from .prepost import InferenceGeometry
     imgs, poses, k = read_scene(scene_dir)
     os.makedirs(out_dir, exist_ok=True)
+    collect = None
+    if save_depth or consistency_check or save_ply:
+        collect = _SceneCollector(out_dir, imgs, poses, k, save_depth, consistency_check, save_ply, int(ply_stride), int(min_views),
+                                  float(px_thr), float(rel_thr))
     skip = ('task', 'min_depth', 'max_depth', 'num_depth_candidates', 'depth_from_argmax', 'pred_bidir_depth', 'intrinsics', 'pose',
             'poses')
     fwd_kw = {key: v for key, v in fwd_kw.items() if key not in skip}
     if pairs_per_launch is not None:
         return _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, inference_size, min_depth, max_depth,
                                    num_depth_candidates, depth_from_argmax, pred_bidir_depth, scale_intrinsics, device,
-                                   int(pairs_per_launch))
+                                   int(pairs_per_launch), collect)
     for i in range(len(imgs) - 1):
         ref, tgt = read_frame_u8(imgs[i])[None].to(device), read_frame_u8(imgs[i + 1])[None].to(device)
         size = tuple(inference_size) if inference_size else nearest_size(ref.shape[1:3], padding_factor)
@@ -77,11 +146,17 @@ def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_si
         write_png8(stem + '.png', rgb[0])
         if pred_bidir_depth:
             write_png8(stem + '_bwd.png', rgb[1])
+        if collect is not None:
+            collect.add(i, depth[0], ref[0])
+            if pred_bidir_depth and i == len(imgs) - 2:
+                collect.add(i + 1, depth[1], tgt[0])
+    if collect is not None:
+        collect.finish()
     return max(0, len(imgs) - 1)
 
 
 def _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, inference_size, min_depth, max_depth,
-                        num_depth_candidates, depth_from_argmax, pred_bidir_depth, scale_intrinsics, device, step):
+                        num_depth_candidates, depth_from_argmax, pred_bidir_depth, scale_intrinsics, device, step, collect=None):
     """The scene through ``forward_sequence(task='depth')`` in pieces of ``step`` pairs (``step + 1`` frames first, then ``step`` frames
     joined by the carry), so that at most ``step + 1`` frames and their predictions are resident."""
     from .io import write_png8
@@ -90,7 +165,7 @@ def _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, 
         raise ValueError('pairs_per_launch must be >= 1')
     if len(imgs) < 2:
         return 0
-    geom = intrinsics = carry = shape = None
+    geom = intrinsics = carry = shape = pending = None
     pose_dev = torch.from_numpy(poses).to(device)                                            # absolute, uploaded once
     lo = 0
     while lo < len(imgs):
@@ -107,7 +182,8 @@ def _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, 
             intrinsics = torch.from_numpy(k)[None].to(device)
             if scale_intrinsics:
                 intrinsics = geom.scaled_intrinsics(intrinsics)
-        frames, = geom.prepare(torch.stack(host, 0).to(device), normalize=True)               # uint8 up, normalised on the device
+        frames_u8 = torch.stack(host, 0).to(device)
+        frames, = geom.prepare(frames_u8, normalize=True)                                    # uint8 up, normalised on the device
         with torch.no_grad():
             out = model.forward_sequence(frames, task='depth', intrinsics=intrinsics, poses=pose_dev[lo:hi], carry=carry,
                                          pairs_per_launch=step, min_depth=1. / max_depth, max_depth=1. / min_depth,
@@ -117,13 +193,24 @@ def _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, 
         first = lo - (0 if lo == 0 else 1)                                                   # the frame of the piece's first pair
         depth = [out['depth']] + ([out['depth_bwd']] if pred_bidir_depth else [])
         n = depth[0].shape[0]
-        rgb = inverse_depth_to_image(geom.restore(torch.cat(depth, 0), 'depth')).cpu().numpy()   # one copy back per piece
+        restored = geom.restore(torch.cat(depth, 0), 'depth')
+        rgb = inverse_depth_to_image(restored).cpu().numpy()                                 # one copy back per piece
         for j in range(n):
             stem = os.path.join(out_dir, os.path.splitext(os.path.basename(imgs[first + j]))[0])
             write_png8(stem + '.png', rgb[j])
             if pred_bidir_depth:
                 write_png8(stem + '_bwd.png', rgb[n + j])
+        if collect is not None:
+            # the frames of the piece's pairs: the carried frame starts the first pair of every piece but the first
+            pending = frames_u8 if first == lo else torch.cat([pending, frames_u8], 0)
+            for j in range(n):
+                collect.add(first + j, restored[j], pending[j])
+            if pred_bidir_depth and hi == len(imgs):
+                collect.add(first + n, restored[2 * n - 1], pending[n])
+            pending = pending[n:n + 1]                                                       # the last frame starts the next piece's first pair
         lo = hi
+    if collect is not None:
+        collect.finish()
     return len(imgs) - 1
 
 
@@ -142,6 +229,13 @@ def main(argv=None):
     ap.add_argument('--scale-intrinsics', action='store_true', help='rescale the intrinsics with the resize (the reference does not)')
     ap.add_argument('--pairs-per-launch', type=int, default=None, metavar='N',
                     help='sequence mode: encode every frame once and match N pairs per launch (frames of one size)')
+    ap.add_argument('--save-depth', action='store_true', help='write <stem>_depth.png: 16-bit millimetres')
+    ap.add_argument('--consistency-check', action='store_true', help='write <stem>_occ.png: 255 where the neighbouring frames disagree')
+    ap.add_argument('--save-ply', default=None, metavar='FILE', help='write the fused, filtered, coloured point cloud of the scene')
+    ap.add_argument('--ply-stride', type=int, default=1, metavar='S', help='every S-th pixel of every row and column goes into the cloud')
+    ap.add_argument('--min-views', type=int, default=1, help='neighbouring frames (of two) that must agree with a pixel to keep it')
+    ap.add_argument('--px-thr', type=float, default=1.0, help='round-trip reprojection error a consistent pixel stays below (pixels)')
+    ap.add_argument('--rel-thr', type=float, default=0.01, help='relative depth error a consistent pixel stays below')
     ap.add_argument('--model-config', default='gmdepth_s1', choices=[k for k, v in CONFIGS.items() if v[1].get('task') == 'depth'])
     ap.add_argument('--weights', default=None, help="checkpoint (the reference's: a state_dict, or {'model': state_dict}); "
                                                     'default: the seeded synthetic weights')
@@ -151,7 +245,9 @@ def main(argv=None):
     n = run_depth(model, args.scene, args.out, fwd_kw, padding_factor=args.padding_factor, inference_size=args.inference_size,
                   min_depth=args.min_depth, max_depth=args.max_depth, num_depth_candidates=args.num_depth_candidates,
                   depth_from_argmax=args.depth_from_argmax, pred_bidir_depth=args.pred_bidir_depth,
-                  scale_intrinsics=args.scale_intrinsics, pairs_per_launch=args.pairs_per_launch)
+                  scale_intrinsics=args.scale_intrinsics, pairs_per_launch=args.pairs_per_launch, save_depth=args.save_depth,
+                  consistency_check=args.consistency_check, save_ply=args.save_ply, ply_stride=args.ply_stride, min_views=args.min_views,
+                  px_thr=args.px_thr, rel_thr=args.rel_thr)
     print(f'{n} frames written to {args.out}')
 
 

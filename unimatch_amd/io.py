@@ -6,6 +6,7 @@ exactly the bytes the reference tools produce.  Pure host code (numpy); nothing 
   write_flo/read_flo   utils/frame_utils.py:10-99  Middlebury .flo  (magic 202021.25 'PIEH', int32 w, h, interleaved fp32 u v)
   write_pfm/read_pfm   utils/file_io.py:60-127     PFM (rows bottom-to-top, negative scale = little endian)
   write/read_kitti_*   utils/frame_utils.py:102-121  KITTI 16-bit PNG: flow (u, v, valid) = 64 * uv + 2^15; disparity * 256
+  write_ply/read_ply   (no reference counterpart)   binary little-endian PLY point cloud: float x y z, uchar red green blue
 """
 import re
 import struct
@@ -184,6 +185,57 @@ def read_png16(filename):
         prev = cur
     arr = out.view('>u2').astype(np.uint16)
     return arr.reshape(h, w) if ch == 1 else arr.reshape(h, w, 3)
+
+
+# ------------------------------------------------------------------ PLY point clouds
+_PLY_XYZ = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
+_PLY_RGB = [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
+_PLY_TYPES = {'<f4': 'float', 'u1': 'uchar'}
+
+
+def write_ply(filename, xyz, rgb=None):
+    """A binary little-endian PLY of the points ``xyz [N, 3]`` (``float x y z``) and, when given, ``rgb [N, 3]`` uint8
+    (``uchar red green blue``): one header, then N packed rows of 12 or 15 bytes."""
+    xyz = np.asarray(xyz)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError(f'xyz must be [N, 3], got {xyz.shape}')
+    fields = _PLY_XYZ + (_PLY_RGB if rgb is not None else [])
+    rows = np.empty(xyz.shape[0], dtype=fields)
+    for j, (name, _) in enumerate(_PLY_XYZ):
+        rows[name] = xyz[:, j]
+    if rgb is not None:
+        rgb = np.asarray(rgb)
+        if rgb.shape != xyz.shape or rgb.dtype != np.uint8:
+            raise ValueError(f'rgb must be uint8 {xyz.shape}, got {rgb.dtype} {rgb.shape}')
+        for j, (name, _) in enumerate(_PLY_RGB):
+            rows[name] = rgb[:, j]
+    header = ['ply', 'format binary_little_endian 1.0', f'element vertex {xyz.shape[0]}']
+    header += [f'property {_PLY_TYPES[kind]} {name}' for name, kind in fields] + ['end_header']
+    with open(filename, 'wb') as f:
+        f.write(('\n'.join(header) + '\n').encode('ascii'))
+        f.write(rows.tobytes())
+
+
+def read_ply(filename):
+    """``(xyz [N, 3] float32, rgb [N, 3] uint8 or None)`` of a file :func:`write_ply` wrote."""
+    with open(filename, 'rb') as f:
+        blob = f.read()
+    end = blob.find(b'end_header\n')
+    if not blob.startswith(b'ply\n') or end < 0:
+        raise ValueError('not a PLY file')
+    lines = blob[:end].decode('ascii').split('\n')
+    if lines[1] != 'format binary_little_endian 1.0':
+        raise ValueError('only binary little-endian PLY files are supported')
+    n = int(next(ln for ln in lines if ln.startswith('element vertex ')).split()[-1])
+    props = [tuple(ln.split()[1:]) for ln in lines if ln.startswith('property ')]
+    xyz_props, rgb_props = [(_PLY_TYPES[k], nm) for nm, k in _PLY_XYZ], [(_PLY_TYPES[k], nm) for nm, k in _PLY_RGB]
+    if props not in (xyz_props, xyz_props + rgb_props):
+        raise ValueError(f'unsupported PLY properties: {props}')
+    fields = _PLY_XYZ + (_PLY_RGB if len(props) == 6 else [])
+    rows = np.frombuffer(blob, dtype=fields, count=n, offset=end + len(b'end_header\n'))
+    xyz = np.stack([rows[name] for name, _ in _PLY_XYZ], 1).astype(np.float32)
+    rgb = np.stack([rows[name] for name, _ in _PLY_RGB], 1) if len(props) == 6 else None
+    return xyz, rgb
 
 
 # ------------------------------------------------------------------ KITTI encodings

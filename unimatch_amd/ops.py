@@ -731,6 +731,78 @@ class HipOps(WorkspaceRegistry):
         _abi.check(self.lib.um_relative_pose_pairs(_ptr(p), _ptr(rel), p.shape[0], _stream()), 'um_relative_pose_pairs')
         return rel
 
+    # ------------------------------------------------------------------ cross-view consistency and point clouds (csrc/geometry.hip)
+    def disp_consistency(self, disp_left, disp_right, alpha=0.01, beta=0.5):
+        """``um_disp_consistency``: left / right occlusion masks ``[B, H, W]`` fp32 in {0, 1} of the disparities ``disp_left``,
+        ``disp_right`` ``[B, H, W]`` (the flow check on ``(-disp_left, 0)`` / ``(disp_right, 0)``, one launch, two taps per pixel)."""
+        dl, dr = disp_left, disp_right
+        if not (dl.is_cuda and dl.dtype == torch.float32 and dl.dim() == 3 and dl.shape[-1] >= 2
+                and dr.shape == dl.shape and dr.dtype == torch.float32 and dr.device == dl.device):
+            raise ValueError(f'disp_consistency: expected two CUDA float32 [B, H, W >= 2] disparities of one shape, got '
+                             f'{tuple(dl.shape)} {dl.dtype} and {tuple(dr.shape)} {dr.dtype}')
+        dl, dr = dl.contiguous(), dr.contiguous()
+        b, h, w = dl.shape
+        occ_l = torch.empty((b, h, w), dtype=torch.float32, device=dl.device)
+        occ_r = torch.empty_like(occ_l)
+        code = self._launch('disp_consistency', lambda: self.lib.um_disp_consistency(
+            _ptr(dl), _ptr(dr), _ptr(occ_l), _ptr(occ_r), b, h, w, float(alpha), float(beta), _stream()))
+        _abi.check(code, 'um_disp_consistency')
+        return occ_l, occ_r
+
+    def depth_consistency(self, depth_ref, depth_src, cam_fwd, cam_inv, px_thr=1.0, rel_thr=0.01, return_errors=False):
+        """``um_depth_consistency``: ``occ [B, H, W]`` fp32 in {0, 1} (and ``err_px``, ``err_rel`` with ``return_errors``) of the metric
+        depths ``depth_ref``, ``depth_src`` ``[B, H, W]`` under the cam records ``cam_fwd``, ``cam_inv`` ``[B, 30]`` of the
+        ref -> src pose and its inverse (the halves of ``depth_cam(..., 1, bidir=True)``)."""
+        a, s = depth_ref, depth_src
+        if not (a.is_cuda and a.dtype == torch.float32 and a.dim() == 3 and s.shape == a.shape and s.dtype == torch.float32
+                and s.device == a.device):
+            raise ValueError(f'depth_consistency: expected two CUDA float32 [B, H, W] depths of one shape, got '
+                             f'{tuple(a.shape)} {a.dtype} and {tuple(s.shape)} {s.dtype}')
+        b, h, w = a.shape
+        for name, cam in (('cam_fwd', cam_fwd), ('cam_inv', cam_inv)):
+            if not (cam.is_cuda and cam.dtype == torch.float32 and tuple(cam.shape) == (b, 30) and cam.device == a.device):
+                raise ValueError(f'depth_consistency: expected {name} as CUDA float32 [{b}, 30], got {tuple(cam.shape)} {cam.dtype}')
+        a, s, cam_fwd, cam_inv = a.contiguous(), s.contiguous(), cam_fwd.contiguous(), cam_inv.contiguous()
+        occ = torch.empty((b, h, w), dtype=torch.float32, device=a.device)
+        err_px = torch.empty_like(occ) if return_errors else None
+        err_rel = torch.empty_like(occ) if return_errors else None
+        code = self._launch('depth_consistency', lambda: self.lib.um_depth_consistency(
+            _ptr(a), _ptr(s), _ptr(cam_fwd), _ptr(cam_inv), _ptr(occ), _ptr(err_px) if return_errors else None,
+            _ptr(err_rel) if return_errors else None, b, h, w, float(px_thr), float(rel_thr), _stream()))
+        _abi.check(code, 'um_depth_consistency')
+        return (occ, err_px, err_rel) if return_errors else occ
+
+    def points_pack(self, depth, cam_world, keep=None, colors=None, min_depth=0., max_depth=float('inf'), stride=1):
+        """``um_points_pack``: ``(xyz [M, 3] fp32, rgb [M, 3] uint8 or None, count)`` -- the world points of the selected pixels of
+        ``depth [B, H, W]`` under ``cam_world [B, 30]`` in ascending ``(b, y, x)`` order, in buffers of ``M`` = every candidate pixel;
+        ``count`` is a one-element int32 tensor ON THE DEVICE holding N: rows ``N..M-1`` are unwritten.  No synchronisation here."""
+        if not (depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 3):
+            raise ValueError(f'points_pack: expected a CUDA float32 [B, H, W] depth, got {tuple(depth.shape)} {depth.dtype}')
+        b, h, w = depth.shape
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError(f'points_pack: stride must be >= 1, got {stride}')
+        if not (cam_world.is_cuda and cam_world.dtype == torch.float32 and tuple(cam_world.shape) == (b, 30)):
+            raise ValueError(f'points_pack: expected cam_world as CUDA float32 [{b}, 30], got {tuple(cam_world.shape)} {cam_world.dtype}')
+        if keep is not None and not (keep.is_cuda and keep.dtype == torch.float32 and keep.shape == depth.shape):
+            raise ValueError(f'points_pack: expected keep as CUDA float32 {tuple(depth.shape)}, got {tuple(keep.shape)} {keep.dtype}')
+        if colors is not None and not (colors.is_cuda and colors.dtype == torch.uint8 and tuple(colors.shape) == (b, h, w, 3)):
+            raise ValueError(f'points_pack: expected colors as CUDA uint8 {(b, h, w, 3)}, got {tuple(colors.shape)} {colors.dtype}')
+        depth, cam_world = depth.contiguous(), cam_world.contiguous()
+        keep = None if keep is None else keep.contiguous()
+        colors = None if colors is None else colors.contiguous()
+        m = b * (-(-h // stride)) * (-(-w // stride))
+        xyz = torch.empty((m, 3), dtype=torch.float32, device=depth.device)
+        rgb = None if colors is None else torch.empty((m, 3), dtype=torch.uint8, device=depth.device)
+        count = torch.empty(1, dtype=torch.int32, device=depth.device)
+        ws = self._ws(self.lib.um_points_workspace_bytes(b, h, w, stride), depth.device)
+        code = self._launch('points_pack', lambda: self.lib.um_points_pack(
+            _ptr(depth), _ptr(cam_world), None if keep is None else _ptr(keep), None if colors is None else _ptr(colors), _ptr(xyz),
+            None if rgb is None else _ptr(rgb), _ptr(count), b, h, w, stride, float(min_depth), float(max_depth), _ptr(ws), ws.numel(),
+            _stream()))
+        _abi.check(code, 'um_points_pack')
+        return xyz, rgb, count
+
     # ------------------------------------------------------------------ encoder helper (outside the hot path)
     def instance_norm(self, x, relu=True, shortcut=None, eps=1e-5):
         """Fused InstanceNorm2d(affine=False) [+ ReLU] [+ shortcut, ReLU] on a contiguous NCHW fp32 map."""

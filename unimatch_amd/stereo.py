@@ -24,12 +24,15 @@ def nearest_size(shape, padding_factor):
 
 
 def run_stereo(model, left_paths, right_paths, out_dir, fwd_kw, padding_factor=16, inference_size=None, pred_bidir_disp=False,
-               pred_right_disp=False, save_pfm_disp=False, batch_size=1, device='cuda'):
+               pred_right_disp=False, save_pfm_disp=False, batch_size=1, device='cuda', lr_check=False):
     """``inference_stereo`` over the pairs ``(left_paths[i], right_paths[i])``: returns the number of pairs written.  Consecutive
-    pairs of one size are predicted ``batch_size`` at a time."""
+    pairs of one size are predicted ``batch_size`` at a time.  ``lr_check``: also the left / right occlusion masks."""
+    from .geometry import disparity_consistency_check
     from .io import write_pfm, write_png8
     if len(left_paths) != len(right_paths):
         raise ValueError(f'{len(left_paths)} left and {len(right_paths)} right images')
+    if lr_check and not pred_bidir_disp:
+        raise ValueError('--lr-check needs --pred-bidir-disp (both views are compared)')
     os.makedirs(out_dir, exist_ok=True)
     fwd_kw = {k: v for k, v in fwd_kw.items() if k != 'task'}
     step = max(1, int(batch_size))
@@ -50,6 +53,9 @@ def run_stereo(model, left_paths, right_paths, out_dir, fwd_kw, padding_factor=1
                                  task='stereo', **fwd_kw)['flow_preds'][-1]                  # [n or 2n, H, W]
         rgb = disparity_to_image(disp).cpu().numpy()
         host = disp.cpu().numpy() if save_pfm_disp else None
+        occ = None
+        if lr_check:
+            occ = [(o.cpu().numpy() * 255.).astype(np.uint8) for o in disparity_consistency_check(disp[:n].contiguous(), disp[n:].contiguous())]
         for j in range(n):
             stem = os.path.join(out_dir, os.path.splitext(os.path.basename(left_paths[done + j]))[0])
             outputs = [('_disp', j)] + ([('_disp_right', n + j)] if pred_bidir_disp else [])
@@ -57,6 +63,9 @@ def run_stereo(model, left_paths, right_paths, out_dir, fwd_kw, padding_factor=1
                 write_png8(stem + suffix + '.png', rgb[row])
                 if save_pfm_disp:
                     write_pfm(stem + suffix + '.pfm', host[row])
+            if occ is not None:
+                write_png8(stem + '_occ.png', occ[0][j])
+                write_png8(stem + '_occ_right.png', occ[1][j])
         done += n
     return done
 
@@ -99,6 +108,7 @@ def main(argv=None):
     ap.add_argument('--pred-bidir-disp', action='store_true')
     ap.add_argument('--pred-right-disp', action='store_true')
     ap.add_argument('--save-pfm-disp', action='store_true')
+    ap.add_argument('--lr-check', action='store_true', help='with --pred-bidir-disp: write the left / right occlusion masks (0 / 255)')
     ap.add_argument('--batch-size', type=int, default=1)
     ap.add_argument('--model-config', default='gmstereo_s1', choices=[k for k, v in CONFIGS.items() if v[1].get('task') == 'stereo'])
     ap.add_argument('--weights', default=None, help="checkpoint (the reference's: a state_dict, or {'model': state_dict}); "
@@ -112,7 +122,7 @@ def main(argv=None):
     model, fwd_kw = load_model(args.model_config, args.weights, args.precision)
     n = run_stereo(model, lefts, rights, args.out, fwd_kw, padding_factor=args.padding_factor, inference_size=args.inference_size,
                    pred_bidir_disp=args.pred_bidir_disp, pred_right_disp=args.pred_right_disp, save_pfm_disp=args.save_pfm_disp,
-                   batch_size=args.batch_size)
+                   batch_size=args.batch_size, lr_check=args.lr_check)
     print(f'{n} pairs written to {args.out}')
 
 
