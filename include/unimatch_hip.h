@@ -569,6 +569,21 @@ int um_fwd_bwd_occlusion(const float* fwd, const float* bwd, float* occ_fwd, flo
 size_t um_flow_to_rgb_workspace_bytes(int batch, int h, int w);
 int um_flow_to_rgb(const float* flow, unsigned char* rgb, int batch, int h, int w, void* workspace, size_t ws_bytes, void* stream);
 
+/* Point tracks (csrc/video.hip): follow n points through the `pairs` consecutive flows of a sequence in one launch, one thread per
+ * track with its position and alive flag in registers.  flow [pairs,2,h,w] fp32 (pair t maps frame t to frame t + 1), occ
+ * [pairs,h,w] fp32 (1 = occluded, the occ_fwd of um_fwd_bwd_occlusion) or NULL.  A track is (x, y) in pixel coordinates of the current
+ * frame; inside(x, y) is 0 <= x <= w - 1 and 0 <= y <= h - 1 (false for a NaN).  It starts at pos_in[i] ([n,2] fp32), or with
+ * pos_in == NULL at point i = ((i % gw) * grid_stride, (i / gw) * grid_stride) of the grid gw = ceil(w / grid_stride), gh =
+ * ceil(h / grid_stride), n == gw * gh (grid_stride is ignored when pos_in is given); alive = alive_in[i] (NULL: all) && inside.  Step t of
+ * an alive track: (u, v) = bilinear sample of flow t at (x, y), o = bilinear sample of occ t at the same (old) position (pixel
+ * coordinates, taps outside the frame add zero); x += u, y += v; alive = inside(x, y) && !(o >= 0.5).  A track that is not alive keeps
+ * its position -- the one of the step that lost it -- and never recovers.  Writes tracks [pairs,n,2] fp32 (8-byte aligned) and visible
+ * [pairs,n] bytes in {0, 1} after every step; the last rows are the state to continue from (as pos_in / alive_in of the next call).
+ * With grid_stride 1, tracks[t] - grid is the dense long-range flow F(0 -> t+1) = F(0 -> t) + flow_warp(F(t -> t+1), F(0 -> t))
+ * (unimatch/geometry.py:41-72).  h, w >= 2; h * w, n, pairs * n, pairs * h * w <= 2^30.  No workspace, no atomics, no state. */
+int um_flow_chain(const float* flow, const float* occ, const float* pos_in, const unsigned char* alive_in, float* tracks,
+                  unsigned char* visible, int pairs, int h, int w, int n, int grid_stride, void* stream);
+
 /* Evaluation metrics (csrc/metrics.hip): the statistics of the reference's validation loops, reduced on the device.  `pred` is the
  * batch as the model returned it, STILL PADDED ([B,2,hp,wp] flow, [B,hp,wp] disparity / depth); ground truth and masks are
  * [B,(2,)h,w] fp32, and ground-truth pixel (y, x) is compared with pred pixel (y + top, x + left): the InputPadder's crop, read in

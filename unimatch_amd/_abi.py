@@ -81,6 +81,7 @@ SIGNATURES = {
     'um_fwd_bwd_occlusion': (_c_int, [_c_void_p] * 4 + [_c_int] * 3 + [ctypes.c_float] * 2 + [_c_void_p]),
     'um_flow_to_rgb_workspace_bytes': (_c_size_t, [_c_int] * 3),
     'um_flow_to_rgb': (_c_int, [_c_void_p] * 2 + [_c_int] * 3 + [_c_void_p, _c_size_t, _c_void_p]),
+    'um_flow_chain': (_c_int, [_c_void_p] * 6 + [_c_int] * 5 + [_c_void_p]),
     'um_flow_metrics_workspace_bytes': (_c_size_t, [_c_int] * 3),
     'um_flow_metrics': (_c_int, [_c_void_p] * 5 + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p]),
     'um_disp_metrics_workspace_bytes': (_c_size_t, [_c_int] * 3),

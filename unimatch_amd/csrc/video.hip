@@ -1,6 +1,6 @@
-// Video post-processing: forward-backward occlusion masks and Middlebury flow colouring.       gfx950 / wave64
+// Video post-processing: forward-backward occlusion masks, Middlebury flow colouring and point tracks.       gfx950 / wave64
 //
-// Both are memory-bound, one thread per pixel (or four), and neither keeps any state between calls:
+// All are memory-bound, one thread per pixel (or four, or per track), and none keeps any state between calls:
 //
 //   um_fwd_bwd_occlusion  forward_backward_consistency_check (unimatch/geometry.py:75-96) in ONE launch: the reference runs two
 //                         grid_sample warps and about a dozen element-wise ATen kernels.  Per pixel and direction: bilinear sample
@@ -10,6 +10,10 @@
 //                         flow_rgb_max_kernel writes one partial maximum radius per workgroup into the workspace (every slot of the
 //                         launch's geometry is rewritten each call: nothing from an earlier call is ever read), flow_rgb_kernel folds
 //                         its image's partials and colours.  No atomics, no arrival counters.
+//   um_flow_chain         follows points through the P flows of a sequence in ONE launch: a thread owns a track and keeps its position
+//                         and alive flag in registers over the P steps, so the state never goes through HBM between steps (a loop of
+//                         torch ops is about a dozen launches per step, each moving the whole state).  No reference code: the step is
+//                         the composition F(0->t+1) = F(0->t) + flow_warp(F(t->t+1), F(0->t)) of unimatch/geometry.py's flow_warp.
 //
 // Rounding follows the reference step by step (NumPy 2 promotion rules): |flow| of the colouring is a float32 square root (rounded
 // once, __fsqrt_rn); the division by (maxrad + float64 eps) and everything after it -- arctan2, the wheel interpolation, floor -- is
@@ -242,5 +246,107 @@ extern "C" int um_flow_to_rgb(const float* flow, unsigned char* rgb, int batch, 
     hipLaunchKernelGGL(flow_rgb_max_kernel, dim3((unsigned)chunks, (unsigned)batch), dim3(256), 0, stream, flow, partial, L, chunks);
     hipLaunchKernelGGL(flow_rgb_kernel, dim3((unsigned)groups, (unsigned)batch), dim3(256), 0, stream, flow, (const float*)partial, rgb,
                        L, chunks, vec);
+    return (int)hipGetLastError();
+}
+
+// ---- point tracks ---------------------------------------------------------------------------------------------------------------
+
+// Bilinear sample of the flow planes c0 / c1 (and of the mask plane m, when there is one) at the pixel position (px, py): zeros
+// outside, the weights and the tap rule of occ_sample without its normalise / un-normalise round trip.
+__device__ __forceinline__ void chain_sample(const float* __restrict__ c0, const float* __restrict__ c1, const float* __restrict__ m,
+                                             int h, int w, float px, float py, float& s0, float& s1, float& sm) {
+    const float fx0 = floorf(px), fy0 = floorf(py);
+    const float fx1 = fx0 + 1.0f, fy1 = fy0 + 1.0f;
+    const float wnw = (fx1 - px) * (fy1 - py), wne = (px - fx0) * (fy1 - py);
+    const float wsw = (fx1 - px) * (py - fy0), wse = (px - fx0) * (py - fy0);
+    // clamped before the int conversion: a position far out of frame (or NaN: fmaxf returns the other operand) must not overflow it;
+    // every clamped tap is outside
+    const int x0 = (int)fminf(fmaxf(fx0, -2.f), (float)w + 1.f), y0 = (int)fminf(fmaxf(fy0, -2.f), (float)h + 1.f);
+    float a0 = 0.f, a1 = 0.f, am = 0.f;
+    auto tap = [&](int yy, int xx, float wt) {       // loads from a clamped address without a branch; only in-frame taps add
+        const bool in = yy >= 0 && yy < h && xx >= 0 && xx < w;
+        const int q = in ? yy * w + xx : 0;
+        const float v0 = c0[q], v1 = c1[q];
+        a0 = in ? a0 + v0 * wt : a0;
+        a1 = in ? a1 + v1 * wt : a1;
+        if (m) {
+            const float vm = m[q];
+            am = in ? am + vm * wt : am;
+        }
+    };
+    tap(y0, x0, wnw);
+    tap(y0, x0 + 1, wne);
+    tap(y0 + 1, x0, wsw);
+    tap(y0 + 1, x0 + 1, wse);
+    s0 = a0;
+    s1 = a1;
+    sm = am;
+}
+
+// 0 <= x <= w - 1 and 0 <= y <= h - 1; false for a NaN
+__device__ __forceinline__ bool chain_inside(float x, float y, int h, int w) {
+    return x >= 0.f && x <= (float)(w - 1) && y >= 0.f && y <= (float)(h - 1);
+}
+
+// one thread per track: tracks[t][i] = position after pair t, visible[t][i] = still alive after pair t.  A lost track keeps the
+// position of the step that lost it and samples nothing more.
+__global__ __launch_bounds__(256) void flow_chain_kernel(const float* __restrict__ flow, const float* __restrict__ occ,
+                                                         const float* __restrict__ pos_in, const unsigned char* __restrict__ alive_in,
+                                                         f32x2* __restrict__ tracks, unsigned char* __restrict__ visible, int pairs,
+                                                         int h, int w, int n, int gw, int stride) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long L = (long)h * w;
+    float x, y;
+    if (pos_in) {
+        x = pos_in[2 * (long)i];
+        y = pos_in[2 * (long)i + 1];
+    } else {
+        const int gy = i / gw;
+        x = (float)((i - gy * gw) * stride);
+        y = (float)(gy * stride);
+    }
+    bool alive = (alive_in ? alive_in[i] != 0 : true) && chain_inside(x, y, h, w);
+    for (int t = 0; t < pairs; ++t) {
+        if (alive) {
+            const float* f = flow + (long)t * 2 * L;
+            float u, v, o;
+            chain_sample(f, f + L, occ ? occ + (long)t * L : nullptr, h, w, x, y, u, v, o);      // the mask at the OLD position
+            x += u;
+            y += v;
+            alive = chain_inside(x, y, h, w) && !(o >= 0.5f);
+        }
+        f32x2 p;
+        p[0] = x;
+        p[1] = y;
+        tracks[(long)t * n + i] = p;
+        visible[(long)t * n + i] = alive ? 1 : 0;
+    }
+}
+
+extern "C" int um_flow_chain(const float* flow, const float* occ, const float* pos_in, const unsigned char* alive_in, float* tracks,
+                             unsigned char* visible, int pairs, int h, int w, int n, int grid_stride, void* stream) {
+    const long lim = 1L << 30;
+    if (!flow || !tracks || !visible || pairs <= 0 || n <= 0 || h < 2 || w < 2 || (long)h * w > lim || n > lim ||
+        (long)pairs * n > lim || (long)pairs * h * w > lim || (uintptr_t)tracks % 8 != 0) {
+        um_set_error("um_flow_chain: bad argument (pairs=%d h=%d w=%d n=%d)", pairs, h, w, n);
+        return UM_ERR_BAD_ARG;
+    }
+    int gw = 1;
+    if (!pos_in) {                                    // the start grid: every grid_stride-th pixel of every grid_stride-th row
+        if (grid_stride < 1 || grid_stride > lim) {
+            um_set_error("um_flow_chain: grid_stride %d (1 ... 2^30 when pos_in is null)", grid_stride);
+            return UM_ERR_BAD_ARG;
+        }
+        gw = (w + grid_stride - 1) / grid_stride;
+        const int gh = (h + grid_stride - 1) / grid_stride;
+        if ((long)gw * gh != n) {
+            um_set_error("um_flow_chain: n=%d, the stride-%d grid of %d x %d has %d x %d points", n, grid_stride, h, w, gh, gw);
+            return UM_ERR_BAD_ARG;
+        }
+    }
+    ScopedKernelTimer timer(UM_K_CONVEX_UPSAMPLE, (hipStream_t)stream);
+    hipLaunchKernelGGL(flow_chain_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, flow, occ, pos_in,
+                       alive_in, reinterpret_cast<f32x2*>(tracks), visible, pairs, h, w, n, gw, grid_stride);
     return (int)hipGetLastError();
 }

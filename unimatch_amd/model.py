@@ -618,7 +618,7 @@ class UniMatch(nn.Module):
     def forward_sequence(self, frames, attn_type=None, attn_splits_list=None, corr_radius_list=None, prop_radius_list=None,
                          num_reg_refine=1, pred_bidir_flow=False, consistency_check=False, colorize=False, pairs_per_launch=8,
                          carry=None, task='flow', intrinsics=None, poses=None, min_depth=1. / 0.5, max_depth=1. / 10,
-                         num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False):
+                         num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, track_points=None):
         """Optical flow of every pair (t, t+1) of a frame sequence ``frames [T, 3, H, W]`` (raw 0..255), each frame encoded ONCE.
 
         The reference's ``inference_flow`` (evaluate_flow.py:640-831) runs the model on each pair, so every interior frame goes through
@@ -632,6 +632,14 @@ class UniMatch(nn.Module):
         ``pred_bidir_flow``, ``'occ_fwd'`` / ``'occ_bwd'`` ``[P, H, W]`` float with ``consistency_check`` (the reference's
         forward_backward_consistency_check) and ``'flow_rgb'`` (``'flow_bwd_rgb'``) ``[P, H, W, 3]`` uint8 with ``colorize`` (its
         flow_to_image, each image normalised by its own maximum).
+
+        ``track_points`` (flow only) follows points of the call's first frame through the sequence (:func:`video.chain_flows`, one
+        launch per chunk right after the chunk's flows): ``'dense'`` (every pixel), an int stride (every stride-th pixel of every
+        stride-th row) or an ``[N, 2]`` tensor of (x, y).  The result gains ``'tracks' [P, N, 2]`` (positions in frame t + 1) and
+        ``'tracks_visible' [P, N]`` bool; with ``pred_bidir_flow`` a track also ends where the chunk's forward occlusion mask covers
+        it (the mask ``consistency_check`` returns, computed once), otherwise only where it leaves the frame.  The carry gains
+        ``'track'`` (the last positions and flags); a later call with that carry and any ``track_points`` other than ``None``
+        continues the same tracks (a tensor of another N raises).  ``None``: no tracking, and no ``'track'`` in the carry.
 
         ``task='depth'``: the depth of every frame t of a posed video from the pair (t, t + 1) -- the one other task whose consecutive
         pairs share a frame (a stereo pair shares nothing with the next one: ``task='stereo'`` raises).  ``frames`` are what
@@ -651,6 +659,8 @@ class UniMatch(nn.Module):
                                       "batch the pairs through forward() / predict()")
         if task not in ('flow', 'depth'):
             raise ValueError(f"task must be 'flow' or 'depth', got {task!r}")
+        if task == 'depth' and track_points is not None:
+            raise ValueError("track_points follows points through optical flow: it needs task='flow'")
         if task == 'depth':
             return self._depth_sequence(frames, attn_type, attn_splits_list, prop_radius_list, num_reg_refine, pred_bidir_flow,
                                         consistency_check, colorize, pairs_per_launch, carry, intrinsics, poses, min_depth, max_depth,
@@ -671,6 +681,9 @@ class UniMatch(nn.Module):
         kw = dict(attn_type=attn_type if attn_type is not None else '', attn_splits_list=attn_splits_list,
                   corr_radius_list=corr_radius_list, prop_radius_list=prop_radius_list, num_reg_refine=num_reg_refine,
                   pred_bidir_flow=pred_bidir_flow, task='flow')
+        track = None                                      # chain_flows' (points, alive, stride) of the next chunk
+        if track_points is not None:
+            track = self._track_start(track_points, carry, frames)
         assert len(attn_splits_list) == len(corr_radius_list) == len(prop_radius_list) == self.num_scales
         import contextlib
         from . import video
@@ -683,7 +696,7 @@ class UniMatch(nn.Module):
             _abi.check_operand_range('an earlier forward of this process: ')
         guard = torch.cuda.device(dev) if frames.is_cuda else contextlib.nullcontext()
         step = int(pairs_per_launch)
-        out = {k: [] for k in ('flow', 'flow_bwd', 'occ_fwd', 'occ_bwd', 'flow_rgb', 'flow_bwd_rgb')}
+        out = {k: [] for k in ('flow', 'flow_bwd', 'occ_fwd', 'occ_bwd', 'flow_rgb', 'flow_bwd_rgb', 'tracks', 'tracks_visible')}
         with guard, torch.no_grad():
             prev = None                                   # per-scale features [1, C, h, w] of the frame before frames[i]
             if carry is not None:
@@ -703,13 +716,20 @@ class UniMatch(nn.Module):
                 prev = [f[f.shape[0] - 1:] for f in feats]
                 fwd = pred[:nb]
                 out['flow'].append(fwd)
+                occ_f = None
                 if pred_bidir_flow:
                     bwd = pred[nb:]
                     out['flow_bwd'].append(bwd)
-                    if consistency_check:
+                    if consistency_check or track is not None:
                         occ_f, occ_b = video.forward_backward_consistency_check(fwd, bwd)
+                    if consistency_check:
                         out['occ_fwd'].append(occ_f)
                         out['occ_bwd'].append(occ_b)
+                if track is not None:
+                    trk, vis = video.chain_flows(fwd, occ_f, *track)
+                    out['tracks'].append(trk)
+                    out['tracks_visible'].append(vis)
+                    track = (trk[-1], vis[-1], 1)
                 if colorize:
                     out['flow_rgb'].append(video.flow_to_image(fwd))
                     if pred_bidir_flow:
@@ -717,7 +737,30 @@ class UniMatch(nn.Module):
             last = frames[frames.shape[0] - 1:]
             result = {k: v[0] if len(v) == 1 else torch.cat(v, 0) for k, v in out.items() if v}
             result['carry'] = {'features': [p.clone() for p in prev], 'frame': last.clone(), 'state': self._carry_state(frames)}
+            if track is not None:
+                result['carry']['track'] = {'points': track[0].clone(), 'alive': track[1].clone()}
         return result
+
+    @staticmethod
+    def _track_start(track_points, carry, frames):
+        """``(points, alive, stride)`` for :func:`video.chain_flows` on the first chunk: the carried tracks when the carry holds some
+        (``track_points`` then only enables tracking), else the start ``track_points`` names."""
+        n = None
+        if torch.is_tensor(track_points):
+            if track_points.dim() != 2 or track_points.shape[1] != 2 or not track_points.is_floating_point():
+                raise ValueError(f'track_points: expected a floating-point [N, 2] tensor of (x, y), got {tuple(track_points.shape)} '
+                                 f'{track_points.dtype}')
+            n = track_points.shape[0]
+        elif track_points != 'dense' and (isinstance(track_points, bool) or not isinstance(track_points, int) or track_points < 1):
+            raise ValueError(f"track_points: expected 'dense', an int stride >= 1 or an [N, 2] tensor, got {track_points!r}")
+        if carry is not None and 'track' in carry:
+            points, alive = carry['track']['points'].to(frames.device), carry['track']['alive'].to(frames.device)
+            if n is not None and n != points.shape[0]:
+                raise ValueError(f'track_points: {n} points, the carry follows {points.shape[0]}')
+            return points, alive, 1
+        if n is not None:
+            return track_points.to(frames.device).float(), None, 1
+        return None, None, 1 if track_points == 'dense' else int(track_points)
 
     def _depth_sequence(self, frames, attn_type, attn_splits_list, prop_radius_list, num_reg_refine, pred_bidir_flow, consistency_check,
                         colorize, pairs_per_launch, carry, intrinsics, poses, min_depth, max_depth, num_depth_candidates,

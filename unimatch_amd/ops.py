@@ -528,6 +528,43 @@ class HipOps(WorkspaceRegistry):
         _abi.check(code, 'um_flow_to_rgb')
         return rgb
 
+    def flow_chain(self, flow, occ=None, points=None, alive=None, stride=1):
+        """``um_flow_chain``: follow points through the flows ``flow [P, 2, H, W]`` of consecutive pairs in one launch ->
+        ``(tracks [P, N, 2] float32, visible [P, N] bool)``.  ``occ [P, H, W]`` (1 = occluded) ends a track whose sample of it reaches
+        0.5; ``points [N, 2]`` as (x, y) (``None``: every ``stride``-th pixel of every ``stride``-th row) and ``alive [N]`` bool are
+        the start -- the last rows of an earlier call continue it."""
+        if not (flow.is_cuda and flow.dtype == torch.float32 and flow.dim() == 4 and flow.shape[1] == 2):
+            raise ValueError(f'flow_chain: flow: expected a CUDA float32 [P, 2, H, W] tensor, got {tuple(flow.shape)} {flow.dtype}')
+        p, _, h, w = flow.shape
+        if occ is not None and not (occ.dtype == torch.float32 and occ.device == flow.device and tuple(occ.shape) == (p, h, w)):
+            raise ValueError(f'flow_chain: occ: expected float32 {(p, h, w)} on {flow.device}, got {tuple(occ.shape)} {occ.dtype} '
+                             f'on {occ.device}')
+        if points is not None:
+            if not (points.dtype == torch.float32 and points.device == flow.device and points.dim() == 2 and points.shape[1] == 2):
+                raise ValueError(f'flow_chain: points: expected float32 [N, 2] on {flow.device}, got {tuple(points.shape)} '
+                                 f'{points.dtype} on {points.device}')
+            n = points.shape[0]
+            points = points.contiguous()
+        else:
+            if int(stride) < 1:
+                raise ValueError(f'flow_chain: stride must be >= 1, got {stride}')
+            n = -(-h // int(stride)) * -(-w // int(stride))
+        if alive is not None:
+            if not (alive.dtype == torch.bool and alive.device == flow.device and tuple(alive.shape) == (n,)):
+                raise ValueError(f'flow_chain: alive: expected bool {(n,)} on {flow.device}, got {tuple(alive.shape)} {alive.dtype} '
+                                 f'on {alive.device}')
+            alive = alive.contiguous().view(torch.uint8)
+        flow = flow.contiguous()
+        occ = None if occ is None else occ.contiguous()
+        tracks = torch.empty((p, n, 2), dtype=torch.float32, device=flow.device)
+        visible = torch.empty((p, n), dtype=torch.uint8, device=flow.device)
+        opt = lambda t: None if t is None else _ptr(t)
+        code = self._launch('flow_chain', lambda: self.lib.um_flow_chain(
+            _ptr(flow), opt(occ), opt(points), opt(alive), _ptr(tracks), _ptr(visible), p, h, w, n, int(stride), _stream()),
+            {'bytes': 21.0 * p * n})
+        _abi.check(code, 'um_flow_chain')
+        return tracks, visible.view(torch.bool)
+
     # ------------------------------------------------------------------ inference-size handling
     @staticmethod
     def _check_sizing(name, mode, size, crop):

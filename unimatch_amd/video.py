@@ -2,14 +2,16 @@
 
   forward_backward_consistency_check(fwd, bwd, alpha, beta)   occlusion masks (unimatch/geometry.py:75-96)
   flow_to_image(flow)                                         Middlebury colouring (utils/flow_viz.py:231-254), per image
+  chain_flows(flow, occ, points, alive, stride)               long-range point tracks through the flows of consecutive pairs
 
-Both run on the HIP kernels (``um_fwd_bwd_occlusion``, ``um_flow_to_rgb``) for CUDA tensors.  For host tensors they run the host
+They run on the HIP kernels (``um_fwd_bwd_occlusion``, ``um_flow_to_rgb``, ``um_flow_chain``) for CUDA tensors.  For host tensors they run the host
 restatement below, written step by step in the dtypes the reference evaluates them in (float32 up to the maximum radius, float64 from
 the normalisation on, as NumPy 2 promotes); the CPU tests pin it against fixtures minted from the reference.
 
 ``python -m unimatch_amd.video --frames DIR --out DIR [...]`` runs :meth:`UniMatch.forward_sequence` over the ``*.png`` / ``*.jpg``
 frames of a directory (sorted) and writes the reference's file set: ``%04d_flow.png``, ``%04d_flow_bwd.png``, ``%04d_occ_fwd.png`` /
-``%04d_occ_bwd.png`` and ``%04d_pred.flo`` (``%04d_pred_bwd.flo``).  Reading frames needs PIL; video containers are not supported.
+``%04d_occ_bwd.png`` and ``%04d_pred.flo`` (``%04d_pred_bwd.flo``); ``--track-grid S`` adds ``tracks.npz``, the tracks of every S-th
+pixel of the first frame through the whole directory.  Reading frames needs PIL; video containers are not supported.
 """
 import argparse
 import glob
@@ -119,6 +121,111 @@ def flow_to_image(flow):
     return out if torch.is_tensor(flow) else out.cpu().numpy()
 
 
+# ------------------------------------------------------------------ point tracks
+def start_grid(h, w, stride=1, device=None):
+    """``[N, 2]`` float32 (x, y) of every ``stride``-th pixel of every ``stride``-th row, row-major: the start of ``points=None``."""
+    ys, xs = torch.meshgrid(torch.arange(0, h, stride, device=device), torch.arange(0, w, stride, device=device), indexing='ij')
+    return torch.stack([xs.reshape(-1), ys.reshape(-1)], -1).float()
+
+
+def _chain_sample(planes, x, y):
+    """Bilinear sample of ``planes [C, H, W]`` at the pixel positions (x, y) ``[N]``: taps outside the frame add zero.  Weights, tap
+    order and the clamp before the integer conversion are those of ``chain_sample`` in csrc/video.hip."""
+    c, h, w = planes.shape
+    flat = planes.reshape(c, h * w)
+    fx0, fy0 = torch.floor(x), torch.floor(y)
+    fx1, fy1 = fx0 + 1.0, fy0 + 1.0
+    wts = ((fx1 - x) * (fy1 - y), (x - fx0) * (fy1 - y), (fx1 - x) * (y - fy0), (x - fx0) * (y - fy0))
+    x0 = torch.where(fx0 == fx0, fx0, torch.full_like(fx0, -2.0)).clamp(-2.0, w + 1.0).long()       # a NaN is outside
+    y0 = torch.where(fy0 == fy0, fy0, torch.full_like(fy0, -2.0)).clamp(-2.0, h + 1.0).long()
+    acc = torch.zeros(c, x.numel(), dtype=planes.dtype)
+    for (dy, dx), wt in zip(((0, 0), (0, 1), (1, 0), (1, 1)), wts):
+        yy, xx = y0 + dy, x0 + dx
+        inside = (yy >= 0) & (yy < h) & (xx >= 0) & (xx < w)
+        q = torch.where(inside, yy * w + xx, torch.zeros_like(yy))
+        acc = torch.where(inside, acc + flat[:, q] * wt, acc)
+    return acc
+
+
+def _chain_flows_host(flow, occ, points, alive):
+    """float32 restatement of ``um_flow_chain``: the documented step, one torch op per operation of the kernel."""
+    p, _, h, w = flow.shape
+    x, y = points[:, 0].clone(), points[:, 1].clone()
+
+    def inside(x, y):
+        return (x >= 0) & (x <= w - 1) & (y >= 0) & (y <= h - 1)
+    alive = alive & inside(x, y)
+    tracks, visible = [], []
+    for t in range(p):
+        uv = _chain_sample(flow[t], x, y)
+        nx, ny = torch.where(alive, x + uv[0], x), torch.where(alive, y + uv[1], y)
+        still = alive & inside(nx, ny)
+        if occ is not None:
+            still = still & ~(_chain_sample(occ[t][None], x, y)[0] >= 0.5)                     # the mask at the OLD position
+        x, y, alive = nx, ny, still
+        tracks.append(torch.stack([x, y], -1))
+        visible.append(alive)
+    return torch.stack(tracks, 0), torch.stack(visible, 0)
+
+
+def chain_flows(flow, occ=None, points=None, alive=None, stride=1):
+    """Follow points through the flows ``flow [P, 2, H, W]`` of ``P`` consecutive frame pairs (pair t maps frame t to frame t + 1)
+    -> ``(tracks [P, N, 2] float32, visible [P, N] bool)``: ``tracks[t]`` are the (x, y) pixel positions in frame t + 1.
+
+    ``points [N, 2]`` as (x, y) in the first frame; ``None`` is the grid of every ``stride``-th pixel of every ``stride``-th row
+    (:func:`start_grid`; ``stride=1``: ``tracks[t] - grid`` is the dense long-range flow from frame 0 to frame t + 1, the composition
+    ``F(0->t+1) = F(0->t) + flow_warp(F(t->t+1), F(0->t))`` of the reference's ``flow_warp``).  ``alive [N]`` bool: tracks to follow
+    (``None``: all).  A point is inside when ``0 <= x <= W - 1`` and ``0 <= y <= H - 1``; a track starts alive when it is inside.  Each
+    step adds the flow sampled bilinearly at the track (pixel coordinates, zeros outside) and the track stays alive while the new
+    position is inside and, with ``occ [P, H, W]`` (1 = occluded, the ``occ_fwd`` of :func:`forward_backward_consistency_check`), the
+    mask sampled at the OLD position is below 0.5.  A lost track keeps its last position and never recovers.  To continue a sequence
+    pass ``points=tracks[-1], alive=visible[-1]``.  CUDA tensors run ``um_flow_chain`` (one launch), host tensors the float32
+    restatement."""
+    if not torch.is_tensor(flow) or flow.dim() != 4 or flow.shape[1] != 2 or flow.shape[0] < 1:
+        raise ValueError(f'flow: expected a [P, 2, H, W] tensor with P >= 1, got {tuple(getattr(flow, "shape", ()))}')
+    if not flow.is_floating_point():
+        raise ValueError(f'flow: expected a floating-point tensor, got {flow.dtype}')
+    p, _, h, w = flow.shape
+    if h < 2 or w < 2:
+        raise ValueError(f'flow: H and W must be >= 2, got {h} x {w}')
+    if occ is not None:
+        if not torch.is_tensor(occ) or tuple(occ.shape) != (p, h, w):
+            raise ValueError(f'occ: expected {(p, h, w)} (one mask per flow), got {tuple(getattr(occ, "shape", ()))}')
+        if not occ.is_floating_point():
+            raise ValueError(f'occ: expected a floating-point mask (1 = occluded), got {occ.dtype}')
+        if occ.device != flow.device:
+            raise ValueError(f'occ: on {occ.device}, flow is on {flow.device}')
+    if points is not None:
+        if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 2 or points.shape[0] < 1:
+            raise ValueError(f'points: expected [N, 2] as (x, y) with N >= 1, got {tuple(getattr(points, "shape", ()))}')
+        if not points.is_floating_point():
+            raise ValueError(f'points: expected a floating-point tensor, got {points.dtype}')
+        if points.device != flow.device:
+            raise ValueError(f'points: on {points.device}, flow is on {flow.device}')
+        n = points.shape[0]
+    else:
+        if isinstance(stride, bool) or not isinstance(stride, int) or stride < 1:
+            raise ValueError(f'stride: expected an int >= 1, got {stride!r}')
+        n = -(-h // stride) * -(-w // stride)
+    if alive is not None:
+        if not torch.is_tensor(alive) or alive.dtype != torch.bool or tuple(alive.shape) != (n,):
+            raise ValueError(f'alive: expected a bool tensor of shape {(n,)}, got {tuple(getattr(alive, "shape", ()))} '
+                             f'{getattr(alive, "dtype", type(alive))}')
+        if alive.device != flow.device:
+            raise ValueError(f'alive: on {alive.device}, flow is on {flow.device}')
+    flow = flow.float()
+    occ = None if occ is None else occ.float()
+    points = None if points is None else points.float()
+    if flow.is_cuda:
+        with torch.cuda.device(flow.device):
+            return _hip().flow_chain(flow, occ, points, alive, stride)
+    if points is None:
+        points = start_grid(h, w, stride)
+    if alive is None:
+        alive = torch.ones(n, dtype=torch.bool)
+    return _chain_flows_host(flow, occ, points, alive)
+
+
 # ------------------------------------------------------------------ frame-directory driver
 def list_frames(directory):
     return sorted(glob.glob(os.path.join(directory, '*.png')) + glob.glob(os.path.join(directory, '*.jpg')))
@@ -143,16 +250,19 @@ def read_frame_u8(path):
 
 
 def run_directory(model, paths, out_dir, fwd_kw, padding_factor=8, inference_size=None, pred_bidir_flow=False, fwd_bwd_check=False,
-                  save_flo=False, pairs_per_launch=8, device='cuda', device_resize=False):
+                  save_flo=False, pairs_per_launch=8, device='cuda', device_resize=False, track_grid=0):
     """``inference_flow`` over the frames ``paths`` with the sequence mode: returns the number of pairs written.  ``device_resize``:
     upload the frames as uint8 and transpose / resize / resize back through :class:`unimatch_amd.prepost.InferenceGeometry` (one
-    launch per step) instead of an fp32 upload and torch ops; the files written have the same names and the same format."""
+    launch per step) instead of an fp32 upload and torch ops; the files written have the same names and the same format.
+    ``track_grid`` S > 0: follow every S-th pixel of the first frame through the restored flows (:func:`chain_flows`, with the forward
+    occlusion mask when ``pred_bidir_flow``) and write ``tracks.npz``: ``tracks [T-1, N, 2]``, ``visible [T-1, N]``, ``start [N, 2]``."""
     from .io import write_flo, write_png8
     from .prepost import InferenceGeometry
     if fwd_bwd_check and not pred_bidir_flow:
         raise ValueError('--fwd-bwd-check needs --pred-bidir-flow (as the reference asserts)')
     os.makedirs(out_dir, exist_ok=True)
     carry, pair = None, 0
+    track, tracks, visible = None, [], []                               # (positions, alive) after the last pair; per-chunk rows
     step = max(1, int(pairs_per_launch))
     i = 0
     while i < len(paths) - (1 if carry is None else 0):
@@ -187,7 +297,16 @@ def run_directory(model, paths, out_dir, fwd_kw, padding_factor=8, inference_siz
         if transpose:
             flows = [f.transpose(-2, -1) for f in flows]
         rgbs = [flow_to_image(f.contiguous()).cpu().numpy() for f in flows]
-        occ = forward_backward_consistency_check(flows[0].contiguous(), flows[1].contiguous()) if fwd_bwd_check else None
+        occ = None
+        if fwd_bwd_check or (track_grid and pred_bidir_flow):
+            occ = forward_backward_consistency_check(flows[0].contiguous(), flows[1].contiguous())
+        if track_grid:
+            trk, vis = chain_flows(flows[0].contiguous(), None if occ is None else occ[0], *(track or (None, None)), stride=track_grid)
+            track = (trk[-1], vis[-1])
+            tracks.append(trk.cpu().numpy())
+            visible.append(vis.cpu().numpy())
+        if not fwd_bwd_check:
+            occ = None
         host = [f.permute(0, 2, 3, 1).cpu().numpy() for f in flows]
         for j in range(host[0].shape[0]):
             name = os.path.join(out_dir, '%04d' % (pair + j))
@@ -202,6 +321,10 @@ def run_directory(model, paths, out_dir, fwd_kw, padding_factor=8, inference_siz
                 if pred_bidir_flow:
                     write_flo(name + '_pred_bwd.flo', host[1][j])
         pair += host[0].shape[0]
+    if track_grid:
+        h, w = host[0].shape[1:3]
+        np.savez(os.path.join(out_dir, 'tracks.npz'), tracks=np.concatenate(tracks, 0), visible=np.concatenate(visible, 0),
+                 start=start_grid(h, w, track_grid).numpy())
     return pair
 
 
@@ -221,6 +344,9 @@ def main(argv=None):
                                                     'default: the seeded synthetic weights')
     ap.add_argument('--precision', default='exact', choices=['exact', 'fast'])
     ap.add_argument('--pairs-per-launch', type=int, default=8)
+    ap.add_argument('--track-grid', type=int, default=0, metavar='S',
+                    help='follow every S-th pixel of the first frame through the sequence and write tracks.npz (0: off); with '
+                         '--pred-bidir-flow a track also ends where the forward occlusion mask covers it')
     ap.add_argument('--device-resize', action='store_true', help='upload uint8 frames; transpose, resize and resize back on the device')
     args = ap.parse_args(argv)
     paths = list_frames(args.frames)
@@ -239,7 +365,7 @@ def main(argv=None):
     fwd_kw = {k: v for k, v in fk.items() if k != 'task'}
     n = run_directory(model, paths, args.out, fwd_kw, padding_factor=args.padding_factor, inference_size=args.inference_size,
                       pred_bidir_flow=args.pred_bidir_flow, fwd_bwd_check=args.fwd_bwd_check, save_flo=args.save_flo,
-                      pairs_per_launch=args.pairs_per_launch, device_resize=args.device_resize)
+                      pairs_per_launch=args.pairs_per_launch, device_resize=args.device_resize, track_grid=args.track_grid)
     print(f'{n} pairs written to {args.out}')
 
 
