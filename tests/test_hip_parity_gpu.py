@@ -831,6 +831,23 @@ def test_cost_volume_planes_equal_the_volume(ops):
         assert torch.equal(pl[:, rows], torch.zeros(2, 96, device=DEV))
 
 
+def test_cost_volume_planes_validate_flow_and_destination(ops):
+    """local_corr_with_flow_planes takes its batch from f0, so it checks ``flow`` against it as local_corr_with_flow does (the
+    refinement block at batch 2B on B feature samples was the silent case), and ``dest`` against the rows the kernel writes.  Only
+    arguments that would be harmless without the check are tried: a flow with MORE samples than f0, a float64 flow, one channel, a
+    destination of another dtype -- every one a ValueError before any launch."""
+    b, h, w = 2, 6, 8
+    f0, f1 = rnd(123, b, h * w, 128).to(DEV), rnd(124, b, h * w, 128).to(DEV)
+    flow = rnd(125, b, 2, h, w).to(DEV)
+    buf = ops.planes_buffer(b * h * w, 96)
+    ops.local_corr_with_flow_planes(f0, f1, flow, h, w, 4, buf, 96)            # the valid call goes through
+    for bad in (torch.cat([flow, flow], 0), flow.double(), flow[:, :1].contiguous()):
+        with pytest.raises(ValueError, match='flow'):
+            ops.local_corr_with_flow_planes(f0, f1, bad, h, w, 4, buf, 96)
+    with pytest.raises(ValueError, match='dest'):
+        ops.local_corr_with_flow_planes(f0, f1, flow, h, w, 4, ops.planes_buffer(b * h * w, 96).view(torch.float16), 96)
+
+
 @pytest.mark.parametrize('hw', [(9, 11), (16, 32)])                # generic kernel; 2-D patch kernel (whole 8 x 32 tiles)
 def test_conv_ex_offsets_and_gates(ops, hw):
     """um_conv2d_ex reading a column slice and writing planes at a column offset (the block's concat-free chaining), and

@@ -559,6 +559,14 @@ class UniMatch(nn.Module):
         out['flow_preds'] = preds
         return out
 
+    def _check_bidir_flow(self, pred_bidir_flow):
+        """``pred_bidir_flow`` with refinement needs two scales: the reference stacks [forward; backward] features only at scale
+        1 (unimatch.py:139-141), so on one scale its refinement meets B feature samples and 2B flows and fails in a ``view``.
+        Raised here, before the encoder or the backend is touched."""
+        if pred_bidir_flow and self.reg_refine and self.num_scales == 1:
+            raise ValueError('pred_bidir_flow=True with reg_refine=True needs num_scales=2: at num_scales=1 the features are never '
+                             'stacked [forward; backward] for the refinement (the reference fails there too)')
+
     def _forward_batch(self, img0, img1, parts, attn_type=None, attn_splits_list=None, corr_radius_list=None,
                        prop_radius_list=None, num_reg_refine=1, pred_bidir_flow=False, task='flow', intrinsics=None,
                        pose=None, min_depth=1. / 0.5, max_depth=1. / 10, num_depth_candidates=64,
@@ -567,6 +575,7 @@ class UniMatch(nn.Module):
         if self.training:
             raise RuntimeError('this module implements inference only: call .eval() '
                                '(training-mode auxiliary outputs of the reference are out of scope)')
+        self._check_bidir_flow(pred_bidir_flow)
         kw = dict(attn_type=attn_type, attn_splits_list=attn_splits_list, corr_radius_list=corr_radius_list,
                   prop_radius_list=prop_radius_list, num_reg_refine=num_reg_refine, pred_bidir_flow=pred_bidir_flow, task=task,
                   intrinsics=intrinsics, pose=pose, min_depth=min_depth, max_depth=max_depth,
@@ -665,6 +674,7 @@ class UniMatch(nn.Module):
             return self._depth_sequence(frames, attn_type, attn_splits_list, prop_radius_list, num_reg_refine, pred_bidir_flow,
                                         consistency_check, colorize, pairs_per_launch, carry, intrinsics, poses, min_depth, max_depth,
                                         num_depth_candidates, depth_from_argmax, pred_bidir_depth)
+        self._check_bidir_flow(pred_bidir_flow)
         if consistency_check and not pred_bidir_flow:
             raise AssertionError('consistency_check needs pred_bidir_flow=True (as the reference asserts)')
         if frames.dim() != 4 or frames.shape[1] != 3:
@@ -891,6 +901,7 @@ class UniMatch(nn.Module):
                      depth_from_argmax=False, pred_bidir_depth=False, pred_out=None):
         """One forward of the given samples on the current stream.  ``pred_out``: a contiguous ``[B, 2, H, W]`` tensor the flow
         prediction may be written to (it is then the returned prediction; a path that cannot do so ignores it)."""
+        self._check_bidir_flow(pred_bidir_flow)
         if pred_bidir_flow:
             assert task == 'flow'
         if task == 'depth':

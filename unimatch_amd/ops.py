@@ -1149,7 +1149,15 @@ class HipOps(WorkspaceRegistry):
         b, l, c = f0.shape
         _check_tokens('f0', f0, tokens=h * w)
         _check_tokens('f1', f1, b, l)
-        flow = flow.contiguous()
+        _check_map('flow', flow, b, h, w)
+        if flow.shape[1] != 2:
+            raise ValueError('flow must have 2 channels')
+        # the kernel writes rows 0 .. b*h*w-1 of both planes and the convolutions read the zero padding row after them
+        if not (torch.is_tensor(dest) and dest.is_cuda and dest.dtype == torch.uint8 and dest.is_contiguous() and ld > 0
+                and dest.numel() // (4 * ld) >= b * l + 1):
+            raise ValueError(f'dest: expected a contiguous CUDA uint8 planes buffer of at least ({b * l} + 1) x {ld} fp16 elements per '
+                             f'plane (planes_buffer(rows, ld)), got {tuple(dest.shape) if torch.is_tensor(dest) else type(dest).__name__} '
+                             f'{getattr(dest, "dtype", None)}')
         feat = self._k4_feat_planes(f0, f1, h, w, radius)
         if feat is not None:
             code = self._launch('local_corr_with_flow', lambda: self.lib.um_local_corr_with_flow_feat(
