@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define UM_VERSION 220
+#define UM_VERSION 220   /* 220 also gained um_global_match_stats_workspace_bytes, um_global_match_stats and um_match_mutual */
 
 #define UM_MODE_EXACT 0
 #define UM_MODE_FAST 1
@@ -466,6 +466,31 @@ float um_global_corr_plane_scale(int channels);
 int um_prop_global_attn_planes(const void* q_planes, const void* k_planes, const float* value, float* out, int batch, int h,
                                int w, int channels, int value_channels, int mode, void* workspace, size_t workspace_bytes,
                                void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Matching confidence: statistics of every row of the matching distribution `prob` that
+ * global_correlation_softmax (unimatch/matching.py:7-36) and global_correlation_softmax_stereo
+ * (matching.py:126-151) return next to the flow / disparity, without forming it (csrc/match_stats.hip).
+ * With p_ij = softmax_j(q_i . k_j / sqrt(C)) over all keys (flow) or over the keys x' <= x of the query's
+ * scanline (stereo), per query i:
+ *   stats[:, 0] max_prob  max_j p_ij
+ *   stats[:, 1] entropy   -sum_j p_ij ln p_ij  (nats, 0 ln 0 = 0)
+ *   stats[:, 2] variance  sum_j p_ij |g_j - mu_i|^2, mu_i = sum_j p_ij g_j, g = pixel coordinates (flow: 2-D; stereo: x), >= 0
+ *   best                  argmax_j p_ij: the key's token index y*w + x (flow) or its column x' (stereo); ties go to the lowest index
+ *   mean (may be NULL)    mu_i - g_i: the flow (2 channels) / minus the disparity (1 channel) of the entry points above
+ * A stereo query at x = 0 has one key: exactly (1, 0, 0).  f0, f1: [B, h*w, C].  stats [B', 3, h, w], best [B', h, w] int32,
+ * mean [B', 2 or 1, h, w]; bidir (flow only) appends the f1 -> f0 direction, B' = 2B; stereo != 0 excludes bidir.
+ * Every element of stats, best and mean is written; nothing is read beyond f0, f1 and the workspace.
+ *
+ * um_match_mutual: mutual[b, i] = 1 iff i' = best_bwd[b, best_fwd[b, i]] lies within `radius` feature pixels of i in both x
+ * and y (radius 0: exact mutual nearest neighbours); an index outside [0, h*w) is no match.  best_*: [B, h, w] token indices.
+ * ------------------------------------------------------------------------------------------- */
+size_t um_global_match_stats_workspace_bytes(int batch, int tokens, int channels, int mode);
+int um_global_match_stats(const float* f0, const float* f1, float* stats, int* best, float* mean,
+                          int batch, int h, int w, int channels, int bidir, int stereo,
+                          int mode, void* workspace, size_t workspace_bytes, void* stream);
+int um_match_mutual(const int* best_fwd, const int* best_bwd, unsigned char* mutual, int batch, int h, int w, int radius,
+                    void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Local-window kernels (fp32 VALU, wavefront-shuffle reductions; `mode` does not apply).

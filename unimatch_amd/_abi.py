@@ -112,6 +112,9 @@ SIGNATURES = {
     'um_prop_global_attn': (_c_int, [_c_void_p] * 4 + [_c_int] * 6 + [_c_void_p, _c_size_t, _c_void_p]),
     'um_global_corr_plane_scale': (ctypes.c_float, [_c_int]),
     'um_prop_global_attn_planes': (_c_int, [_c_void_p] * 4 + [_c_int] * 6 + [_c_void_p, _c_size_t, _c_void_p]),
+    'um_global_match_stats_workspace_bytes': (_c_size_t, [_c_int] * 4),
+    'um_global_match_stats': (_c_int, [_c_void_p] * 5 + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p]),
+    'um_match_mutual': (_c_int, [_c_void_p] * 3 + [_c_int] * 4 + [_c_void_p]),
     'um_local_corr_softmax': (_c_int, [_c_void_p] * 3 + [_c_int] * 6 + [_c_void_p]),
     'um_local_corr_with_flow': (_c_int, [_c_void_p] * 4 + [_c_int] * 5 + [_c_void_p]),
     'um_local_corr_with_flow_dilated': (_c_int, [_c_void_p] * 4 + [_c_int] * 6 + [_c_void_p]),

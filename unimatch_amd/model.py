@@ -32,6 +32,7 @@ from .refine import BasicUpdateBlock, convex_upsample
 from .refine_nhwc import NhwcUpdateBlock
 from .dist import shard_batch, shard_bounds
 from .streams import PartRunner, forward_parts
+from .confidence import match_confidence
 
 _IMAGENET_MEAN = (0.485, 0.456, 0.406)
 _IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -481,6 +482,26 @@ class UniMatch(nn.Module):
                                    num_reg_refine, pred_bidir_flow, task, intrinsics, pose, min_depth, max_depth, num_depth_candidates,
                                    depth_from_argmax, pred_bidir_depth)
 
+    def forward_with_confidence(self, img0, img1, **forward_kw):
+        """:meth:`forward` plus ``'match_confidence'``: how sure the global matching step (``corr_radius == -1``) is of every
+        feature pixel's match, from the same tokens the flow is matched on (``unimatch_amd.confidence``: statistics of the reference's
+        ``prob``, which is never formed).  A dict of ``max_prob``, ``entropy``, ``variance`` ``[B', h, w]`` float, ``best``
+        ``[B', h, w]`` int32 (token index; stereo: column), ``scale`` (the map's stride in image pixels) and, with
+        ``pred_bidir_flow=True`` (``B' = 2B``: forward, then backward), ``mutual`` ``[B, h, w]`` bool.  Tasks ``'flow'`` and
+        ``'stereo'``.  The batch runs as one forward; ``flow_preds`` is what :meth:`forward` returns with ``launch_parts = 1``."""
+        task = forward_kw.get('task', 'flow')
+        if task == 'depth':
+            raise NotImplementedError("forward_with_confidence: task='depth' matches by a plane sweep over depth candidates, which has "
+                                      "its own distribution; only 'flow' and 'stereo' have the global matching step")
+        if -1 not in (forward_kw.get('corr_radius_list') or ()):
+            raise ValueError('forward_with_confidence needs a global matching step (a corr_radius of -1 in corr_radius_list)')
+        if forward_kw.get('pred_bidir_flow') and task != 'flow':
+            raise ValueError(f"pred_bidir_flow is a flow option, got task={task!r}")
+        conf = {}
+        out = dict(self._forward_batch(img0, img1, 1, confidence=conf, **forward_kw))
+        out['match_confidence'] = conf
+        return out
+
     _PREDICT_DEFAULTS = {'flow': (8, 'sintel', 'flow'), 'stereo': (32, 'sintel', 'disparity'), 'depth': (16, 'kitti', 'depth')}
 
     def predict(self, img0, img1, *, inference_size=None, padding_factor=None, pad_mode=None, transpose='auto', normalize=None,
@@ -570,8 +591,9 @@ class UniMatch(nn.Module):
     def _forward_batch(self, img0, img1, parts, attn_type=None, attn_splits_list=None, corr_radius_list=None,
                        prop_radius_list=None, num_reg_refine=1, pred_bidir_flow=False, task='flow', intrinsics=None,
                        pose=None, min_depth=1. / 0.5, max_depth=1. / 10, num_depth_candidates=64,
-                       depth_from_argmax=False, pred_bidir_depth=False, **kwargs):
-        """:meth:`forward` with ``parts`` in place of ``launch_parts`` (``ConcurrentUniMatch`` forces its own count here)."""
+                       depth_from_argmax=False, pred_bidir_depth=False, confidence=None, **kwargs):
+        """:meth:`forward` with ``parts`` in place of ``launch_parts`` (``ConcurrentUniMatch`` forces its own count here).
+        ``confidence``: a dict the global matching step fills (:meth:`forward_with_confidence`; one part only)."""
         if self.training:
             raise RuntimeError('this module implements inference only: call .eval() '
                                '(training-mode auxiliary outputs of the reference are out of scope)')
@@ -583,7 +605,8 @@ class UniMatch(nn.Module):
         batch = img0.shape[0]
         parts = self._plan_parts(parts, task, attn_type, batch, img0.shape[-2], img0.shape[-1], img0.is_cuda)
         if parts <= 1:
-            return self._forward_one(img0, img1, **kw)
+            return self._forward_one(img0, img1, confidence=confidence, **kw)
+        assert confidence is None, 'the matching confidence is collected by one forward of the whole batch'
 
         def prepare(r):
             pk = dict(kw, intrinsics=shard_batch(intrinsics, r, parts), pose=shard_batch(pose, r, parts))
@@ -627,7 +650,8 @@ class UniMatch(nn.Module):
     def forward_sequence(self, frames, attn_type=None, attn_splits_list=None, corr_radius_list=None, prop_radius_list=None,
                          num_reg_refine=1, pred_bidir_flow=False, consistency_check=False, colorize=False, pairs_per_launch=8,
                          carry=None, task='flow', intrinsics=None, poses=None, min_depth=1. / 0.5, max_depth=1. / 10,
-                         num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, track_points=None):
+                         num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, track_points=None,
+                         return_confidence=False):
         """Optical flow of every pair (t, t+1) of a frame sequence ``frames [T, 3, H, W]`` (raw 0..255), each frame encoded ONCE.
 
         The reference's ``inference_flow`` (evaluate_flow.py:640-831) runs the model on each pair, so every interior frame goes through
@@ -650,6 +674,10 @@ class UniMatch(nn.Module):
         ``'track'`` (the last positions and flags); a later call with that carry and any ``track_points`` other than ``None``
         continues the same tracks (a tensor of another N raises).  ``None``: no tracking, and no ``'track'`` in the carry.
 
+        ``return_confidence`` (flow only): the result gains ``'match_confidence'``, what :meth:`forward_with_confidence` returns, taken
+        in the same forward at the chunk's global matching step: ``max_prob``, ``entropy``, ``variance``, ``best`` ``[P, h, w]`` of
+        the forward direction, ``scale`` and, with ``pred_bidir_flow``, ``mutual`` ``[P, h, w]``.  A chunk then runs as one part.
+
         ``task='depth'``: the depth of every frame t of a posed video from the pair (t, t + 1) -- the one other task whose consecutive
         pairs share a frame (a stereo pair shares nothing with the next one: ``task='stereo'`` raises).  ``frames`` are what
         :meth:`forward` takes for depth (normalised already), ``poses [T, 4, 4]`` the frames' absolute camera-to-world matrices and
@@ -670,6 +698,10 @@ class UniMatch(nn.Module):
             raise ValueError(f"task must be 'flow' or 'depth', got {task!r}")
         if task == 'depth' and track_points is not None:
             raise ValueError("track_points follows points through optical flow: it needs task='flow'")
+        if task == 'depth' and return_confidence:
+            raise NotImplementedError("return_confidence: task='depth' matches by a plane sweep, which has its own distribution")
+        if return_confidence and -1 not in (corr_radius_list or ()):
+            raise ValueError('return_confidence needs a global matching step (a corr_radius of -1 in corr_radius_list)')
         if task == 'depth':
             return self._depth_sequence(frames, attn_type, attn_splits_list, prop_radius_list, num_reg_refine, pred_bidir_flow,
                                         consistency_check, colorize, pairs_per_launch, carry, intrinsics, poses, min_depth, max_depth,
@@ -707,6 +739,7 @@ class UniMatch(nn.Module):
         guard = torch.cuda.device(dev) if frames.is_cuda else contextlib.nullcontext()
         step = int(pairs_per_launch)
         out = {k: [] for k in ('flow', 'flow_bwd', 'occ_fwd', 'occ_bwd', 'flow_rgb', 'flow_bwd_rgb', 'tracks', 'tracks_visible')}
+        confs = []                                        # per chunk: the matching step's confidence dict
         with guard, torch.no_grad():
             prev = None                                   # per-scale features [1, C, h, w] of the frame before frames[i]
             if carry is not None:
@@ -722,7 +755,10 @@ class UniMatch(nn.Module):
                 chunk = [([] if prev is None else [p]) + [f] for p, f in zip(prev or feats, feats)]
                 nb = new.shape[0] - (1 if prev is None else 0)
                 i += new.shape[0]
-                pred = self._match_pairs(chunk, nb, kw)
+                conf = {} if return_confidence else None
+                pred = self._match_pairs(chunk, nb, kw, confidence=conf)
+                if conf is not None:
+                    confs.append({k: v if k in ('scale', 'mutual') else v[:nb] for k, v in conf.items()})
                 prev = [f[f.shape[0] - 1:] for f in feats]
                 fwd = pred[:nb]
                 out['flow'].append(fwd)
@@ -746,6 +782,8 @@ class UniMatch(nn.Module):
                         out['flow_bwd_rgb'].append(video.flow_to_image(bwd))
             last = frames[frames.shape[0] - 1:]
             result = {k: v[0] if len(v) == 1 else torch.cat(v, 0) for k, v in out.items() if v}
+            if confs:
+                result['match_confidence'] = {k: confs[0][k] if k == 'scale' else torch.cat([c[k] for c in confs], 0) for k in confs[0]}
             result['carry'] = {'features': [p.clone() for p in prev], 'frame': last.clone(), 'state': self._carry_state(frames)}
             if track is not None:
                 result['carry']['track'] = {'points': track[0].clone(), 'alive': track[1].clone()}
@@ -856,12 +894,13 @@ class UniMatch(nn.Module):
                                'pose': pose_all[-1:].clone(), 'intrinsics': k_all[-1:].clone()}
         return result
 
-    def _match_pairs(self, chunk, nb, kw, intrinsics=None, pose=None):
+    def _match_pairs(self, chunk, nb, kw, intrinsics=None, pose=None, confidence=None):
         """The match step (task ``kw['task']``) of the ``nb`` pairs of consecutive frames whose features are ``chunk[s]`` (per scale, a
         list of pieces ``[N_i, C, h, w]`` that together hold the ``nb + 1`` frames in order) -> predictions ``[bidir * nb, ...]`` in the
         reference's [forward; backward] order.  The stream ``[F[lo:hi]; F[lo+1:hi+1]]`` of pairs lo .. hi-1 is ONE concatenation per
         scale.  ``intrinsics [nb, 3, 3]``, ``pose [nb, 4, 4]`` (depth): per pair, sliced with the features.  Where
-        ``streams.forward_parts`` says so, the pairs run as concurrent parts on the process-wide side streams (``streams.PartRunner``)."""
+        ``streams.forward_parts`` says so, the pairs run as concurrent parts on the process-wide side streams (``streams.PartRunner``);
+        with ``confidence`` (the dict ``_match`` fills) they run as one part."""
         def frames_of(pieces, a, b):                  # the pieces that hold frames a .. b-1 of the chunk
             out, base = [], 0
             for t in pieces:
@@ -881,8 +920,8 @@ class UniMatch(nn.Module):
         h8, w8 = ref.shape[-2:]
         parts = self._plan_parts(self.launch_parts, kw['task'], kw['attn_type'], nb, self.upsample_factor * h8, self.upsample_factor * w8,
                                  ref.is_cuda)
-        if parts <= 1:
-            return self._match(stream(0, nb), nb, intrinsics=intrinsics, pose=pose, **kw)['flow_preds'][0]
+        if parts <= 1 or confidence is not None:
+            return self._match(stream(0, nb), nb, intrinsics=intrinsics, pose=pose, confidence=confidence, **kw)['flow_preds'][0]
 
         def prepare(r):
             lo, hi = shard_bounds(nb, r, parts)
@@ -898,7 +937,7 @@ class UniMatch(nn.Module):
     def _forward_one(self, img0, img1, attn_type=None, attn_splits_list=None, corr_radius_list=None,
                      prop_radius_list=None, num_reg_refine=1, pred_bidir_flow=False, task='flow', intrinsics=None,
                      pose=None, min_depth=1. / 0.5, max_depth=1. / 10, num_depth_candidates=64,
-                     depth_from_argmax=False, pred_bidir_depth=False, pred_out=None):
+                     depth_from_argmax=False, pred_bidir_depth=False, pred_out=None, confidence=None):
         """One forward of the given samples on the current stream.  ``pred_out``: a contiguous ``[B, 2, H, W]`` tensor the flow
         prediction may be written to (it is then the returned prediction; a path that cannot do so ignores it)."""
         self._check_bidir_flow(pred_bidir_flow)
@@ -940,7 +979,7 @@ class UniMatch(nn.Module):
                                corr_radius_list=corr_radius_list, prop_radius_list=prop_radius_list, num_reg_refine=num_reg_refine,
                                pred_bidir_flow=pred_bidir_flow, task=task, intrinsics=intrinsics, pose=pose, min_depth=min_depth,
                                max_depth=max_depth, num_depth_candidates=num_depth_candidates, depth_from_argmax=depth_from_argmax,
-                               pred_bidir_depth=pred_bidir_depth)
+                               pred_bidir_depth=pred_bidir_depth, confidence=confidence)
 
     def _encode(self, images, task='flow', position=None):
         """The encode step: the CNN encoder of the images of the tuple ``images``, stacked in that order -> per-scale feature maps
@@ -967,10 +1006,12 @@ class UniMatch(nn.Module):
 
     def _match(self, feats, nb, attn_type='', attn_splits_list=None, corr_radius_list=None, prop_radius_list=None, num_reg_refine=1,
                pred_bidir_flow=False, task='flow', intrinsics=None, pose=None, min_depth=1. / 0.5, max_depth=1. / 10,
-               num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, stream_has_pos=False, pred_out=None):
+               num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, stream_has_pos=False, pred_out=None,
+               confidence=None):
         """The match step: everything after the encoder, on per-scale features ``feats[s] = [f0; f1]`` (``[2 nb, C, h, w]``, the
         first images of the ``nb`` pairs, then the second ones).  ``stream_has_pos``: the encoder added the position table already
-        (``_forward_one`` decides; one scale, no refinement).  ``pred_out``: see ``_forward_one``."""
+        (``_forward_one`` decides; one scale, no refinement).  ``pred_out``: see ``_forward_one``.  ``confidence``: a dict that receives
+        ``confidence.match_confidence`` of the tokens the global matching step (``corr_radius == -1``) matches."""
         ops = self.ops
         dev = feats[0].device
         flow, pred = None, None
@@ -1034,6 +1075,8 @@ class UniMatch(nn.Module):
             else:
                 radius = corr_radius_list[s]
                 if radius == -1:
+                    if confidence is not None and task in ('flow', 'stereo'):
+                        confidence.update(match_confidence(tok0, tok1, h, w, task, pred_bidir_flow, up, getattr(ops, 'precision', 'exact')))
                     if task == 'flow':
                         flow_pred = ops.global_corr_softmax_flow(tok0, tok1, h, w, pred_bidir_flow)
                     elif task == 'stereo':

@@ -250,12 +250,14 @@ def read_frame_u8(path):
 
 
 def run_directory(model, paths, out_dir, fwd_kw, padding_factor=8, inference_size=None, pred_bidir_flow=False, fwd_bwd_check=False,
-                  save_flo=False, pairs_per_launch=8, device='cuda', device_resize=False, track_grid=0):
+                  save_flo=False, pairs_per_launch=8, device='cuda', device_resize=False, track_grid=0, save_confidence=False):
     """``inference_flow`` over the frames ``paths`` with the sequence mode: returns the number of pairs written.  ``device_resize``:
     upload the frames as uint8 and transpose / resize / resize back through :class:`unimatch_amd.prepost.InferenceGeometry` (one
     launch per step) instead of an fp32 upload and torch ops; the files written have the same names and the same format.
     ``track_grid`` S > 0: follow every S-th pixel of the first frame through the restored flows (:func:`chain_flows`, with the forward
-    occlusion mask when ``pred_bidir_flow``) and write ``tracks.npz``: ``tracks [T-1, N, 2]``, ``visible [T-1, N]``, ``start [N, 2]``."""
+    occlusion mask when ``pred_bidir_flow``) and write ``tracks.npz``: ``tracks [T-1, N, 2]``, ``visible [T-1, N]``, ``start [N, 2]``.
+    ``save_confidence``: also write ``<stem>_conf.png``, the peak matching probability of every feature pixel
+    (``forward_sequence(return_confidence=True)``: taken in the same forward) nearest-upsampled to the frame and coloured."""
     from .io import write_flo, write_png8
     from .prepost import InferenceGeometry
     if fwd_bwd_check and not pred_bidir_flow:
@@ -284,8 +286,17 @@ def run_directory(model, paths, out_dir, fwd_kw, padding_factor=8, inference_siz
             size = tuple(inference_size) if inference_size else tuple(int(np.ceil(s / padding_factor)) * padding_factor for s in ori)
             if size != ori:
                 frames = F.interpolate(frames, size=size, mode='bilinear', align_corners=True)
-        out = model.forward_sequence(frames, pred_bidir_flow=pred_bidir_flow, pairs_per_launch=step, carry=carry, **fwd_kw)
+        seq_kw = dict(fwd_kw, return_confidence=True) if save_confidence else fwd_kw
+        out = model.forward_sequence(frames, pred_bidir_flow=pred_bidir_flow, pairs_per_launch=step, carry=carry, **seq_kw)
         carry = out['carry']
+        conf_rgb = None
+        if save_confidence:                                             # taken in the same forward, at the matching step
+            from .confidence import confidence_to_image
+            conf = out['match_confidence']['max_prob']
+            if transpose or (geom is not None and geom.transpose):
+                conf = conf.transpose(-2, -1)
+            shape = geom.shape if geom is not None else (ori[::-1] if transpose else ori)
+            conf_rgb = confidence_to_image(conf, shape).cpu().numpy()
         flows = [out['flow']] + ([out['flow_bwd']] if pred_bidir_flow else [])
         if geom is not None:
             flows = [geom.restore(f, 'flow') for f in flows]
@@ -316,6 +327,8 @@ def run_directory(model, paths, out_dir, fwd_kw, padding_factor=8, inference_siz
             if occ is not None:
                 write_png8(name + '_occ_fwd.png', (occ[0][j].cpu().numpy() * 255.).astype(np.uint8))
                 write_png8(name + '_occ_bwd.png', (occ[1][j].cpu().numpy() * 255.).astype(np.uint8))
+            if conf_rgb is not None:
+                write_png8(name + '_conf.png', conf_rgb[j])
             if save_flo:
                 write_flo(name + '_pred.flo', host[0][j])
                 if pred_bidir_flow:
@@ -347,6 +360,8 @@ def main(argv=None):
     ap.add_argument('--track-grid', type=int, default=0, metavar='S',
                     help='follow every S-th pixel of the first frame through the sequence and write tracks.npz (0: off); with '
                          '--pred-bidir-flow a track also ends where the forward occlusion mask covers it')
+    ap.add_argument('--save-confidence', action='store_true',
+                    help='write <stem>_conf.png: the peak matching probability of every feature pixel, nearest-upsampled to the frame')
     ap.add_argument('--device-resize', action='store_true', help='upload uint8 frames; transpose, resize and resize back on the device')
     args = ap.parse_args(argv)
     paths = list_frames(args.frames)
@@ -365,7 +380,8 @@ def main(argv=None):
     fwd_kw = {k: v for k, v in fk.items() if k != 'task'}
     n = run_directory(model, paths, args.out, fwd_kw, padding_factor=args.padding_factor, inference_size=args.inference_size,
                       pred_bidir_flow=args.pred_bidir_flow, fwd_bwd_check=args.fwd_bwd_check, save_flo=args.save_flo,
-                      pairs_per_launch=args.pairs_per_launch, device_resize=args.device_resize, track_grid=args.track_grid)
+                      pairs_per_launch=args.pairs_per_launch, device_resize=args.device_resize, track_grid=args.track_grid,
+                      save_confidence=args.save_confidence)
     print(f'{n} pairs written to {args.out}')
 
 
