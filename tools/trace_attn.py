@@ -1,5 +1,5 @@
 """Diagnostic: section-level cycle stamps of the attention layer kernel (needs a -DUM_TRACE build:
-``python -m unimatch_amd.build --variant trace -DUM_TRACE [-DUM_WATTN_PIPE_DEFAULT=1]``, then ``UM_LIB=.../libtrace.so``).
+``python -m unimatch_amd.build --variant trace -DUM_TRACE --only window_attn.hip``, then ``UM_LIB=.../libtrace.so``).
 Config-2 geometry at batch 8 (16 streams, 64 x 96 map, 32 x 48 windows) through um_window_attn_qproj_merge_fwd; every 37th
 workgroup stamps s_memtime at the section boundaries of its first 24 key tiles."""
 import ctypes, os, sys

@@ -181,6 +181,79 @@ __device__ __forceinline__ f32x4 ld_agent_16B(const float* p) {
     return a;
 }
 
+// ---- reductions over the 64 lanes of a wave (butterfly: every lane ends up with the result) ----------------------------------
+__device__ __forceinline__ int wave_min_i(int v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = min(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ __forceinline__ int wave_max_i(int v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = max(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ __forceinline__ float wave_max_f(float v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ __forceinline__ float wave_sum_f(float v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// ---- LDS-DMA: 16 (or 4) bytes per lane, global -> LDS without passing through VGPRs --------------------------------------------
+// global_load_lds_* writes lane-linear: LDS address = M0 (wave-uniform destination) + size * lane; the source is a scalar base +
+// a per-lane 32-bit byte offset (or, um_lds_dma16_ptr, a per-lane 64-bit pointer).
+//   * Inline asm on purpose: hipcc cannot prove that the ring slot being filled and the slot being read do not alias and would
+//     drain the DMA (s_waitcnt vmcnt(0)) in front of the next LDS read; hidden from its scoreboard, the transfer stays in flight
+//     for the whole tile.
+//   * M0: hipcc manages M0 itself for its own users, so every statement saves M0, sets it, and restores it: M0 is unchanged
+//     across the helper and nothing is declared clobbered.
+//   * The caller owes the wait: `s_waitcnt vmcnt(0)` (asm, with a "memory" clobber) before the barrier that publishes the slot --
+//     the compiler does not know that the statement wrote LDS.
+// gsv4_kernel (global_match.hip) keeps a form of its own next to the kernel: it forms M0 by s_add of a base and an immediate in
+// the statement, saves / restores nothing and DECLARES M0 clobbered -- one scalar instruction per piece in its pinned MFMA gaps
+// instead of three.  (Undeclared, that M0 write was part of round 5's allocation-dependent wrong results: DESIGN.md section 4.1.)
+__device__ __forceinline__ unsigned um_lds_addr(const unsigned char* p) {          // wave-uniform 32-bit LDS address of p
+    return __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(const __attribute__((address_space(3))) unsigned char*)p);
+}
+// the LDS destination as an ADDRESS (an SGPR value): a flat pointer into the LDS array costs an address-space cast with its null
+// check (s_add_u32 / s_addc_u32 / s_cmp_lg_u64 / s_cselect_b32) per statement; base address + constant costs one s_add
+__device__ __forceinline__ void um_lds_dma16_at(const void* base, unsigned byte_off, unsigned lds_addr) {
+    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);         // (uniform already; folds away when the compiler can prove it)
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(byte_off), "s"(base), "s"(lds_addr)
+                 : "memory");
+}
+__device__ __forceinline__ void um_lds_dma16(const void* base, unsigned byte_off, const unsigned char* lds_dst) {
+    const unsigned dst = um_lds_addr(lds_dst);
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(byte_off), "s"(base), "s"(dst)
+                 : "memory");
+}
+__device__ __forceinline__ void um_lds_dma4(const void* base, unsigned byte_off, const unsigned char* lds_dst) {
+    const unsigned dst = um_lds_addr(lds_dst);
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(byte_off), "s"(base), "s"(dst)
+                 : "memory");
+}
+__device__ __forceinline__ void um_lds_dma16_ptr(const void* gsrc, const unsigned char* lds_dst) {      // per-lane 64-bit source
+    const unsigned dst = um_lds_addr(lds_dst);
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(gsrc), "s"(dst)
+                 : "memory");
+}
+
 // XCD-aware remap of a linear workgroup id: the dispatcher places consecutive ids on consecutive
 // XCDs (id % 8); this gives every XCD a contiguous range of logical ids so that workgroups sharing
 // K/V (query tiles of one window) hit the same L2.  Bijective for any total.  Speed only.

@@ -26,11 +26,6 @@
 //                      all nine taps (the default for every 3x3 layer of the encoder and the refinement block)
 #include <cstdlib>
 #include <cstring>
-// -DUM_CONV_2P=1|2 (diagnostic builds: profiles/r04_precision_budget_conv.txt): two MFMA products instead of three -- 1 drops
-// W_lo . A_hi (weights effectively rounded to one fp16 plane), 2 drops W_hi . A_lo (activations in one plane).
-#ifndef UM_CONV_2P
-#define UM_CONV_2P 0
-#endif
 #include "common.h"
 #include "planes.h"
 
@@ -76,16 +71,6 @@ struct ConvArgs {
     const float* nstats;
     int norm_relu;
 };
-
-__device__ __forceinline__ void conv_dma16(const void* base, unsigned byte_off, const unsigned char* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane(
-        (unsigned)(unsigned long)(const __attribute__((address_space(3))) unsigned char*)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(byte_off), "s"(base), "s"(dst)
-                 : "memory");
-}
 
 // ---- epilogue shared by all kernels: lane holds, for pixel rloc0 + (lane & 31) of image bt (rloc0 = the wave's first pixel,
 // nvalid <= 32 of its pixels exist; part0 = statistics part of the workgroup's first four waves), outputs
@@ -428,7 +413,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const ConvEntryArgs
                 const int sc = dcp ^ ((r >> 2) & 3);
                 const unsigned off = rowoff[i] + (unsigned)((c0 + 8 * sc) * 2);
 #pragma unroll
-                for (int pl = 0; pl < NS; ++pl) conv_dma16(a.ap + pl * a.a_plane_stride, off, buf + pl * TILE + (32 * wave + 16 * i) * 64);
+                for (int pl = 0; pl < NS; ++pl) um_lds_dma16(a.ap + pl * a.a_plane_stride, off, buf + pl * TILE + (32 * wave + 16 * i) * 64);
             }
         }
         // the weight tile is 2 NT blocks of 16 rows; block j goes to wave j mod 4 (every wave issues its share)
@@ -442,7 +427,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const ConvEntryArgs
                 const unsigned off = (unsigned)(((long)n * ktot + kglob + 8 * sc) * 2);
 #pragma unroll
                 for (int pl = 0; pl < NS; ++pl)
-                    conv_dma16(a.wp + pl * a.w_plane_stride, off, buf + NS * TILE + pl * WTILE + (16 * j) * 64);
+                    um_lds_dma16(a.wp + pl * a.w_plane_stride, off, buf + NS * TILE + pl * WTILE + (16 * j) * 64);
             }
         }
     };
@@ -585,8 +570,8 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const ConvEntryArgs
                 const i16x8 wh = *reinterpret_cast<const i16x8*>(wt + nt * 32 * 64 + foff[ks]);
                 if (NS == 2) {
                     const i16x8 wl = *reinterpret_cast<const i16x8*>(wt + WTILE + nt * 32 * 64 + foff[ks]);
-                    if (UM_CONV_2P != 1) acc[nt] = T::mfma(wl, bh, acc[nt]);
-                    if (UM_CONV_2P != 2) acc[nt] = T::mfma(wh, bl, acc[nt]);
+                    acc[nt] = T::mfma(wl, bh, acc[nt]);
+                    acc[nt] = T::mfma(wh, bl, acc[nt]);
                 }
                 acc[nt] = T::mfma(wh, bh, acc[nt]);
             }
@@ -595,8 +580,8 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const ConvEntryArgs
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) {
                         if (NS == 2) {
-                            if (UM_CONV_2P != 1) acc2[nt] = T::mfma(pwl[nt], bh, acc2[nt]);
-                            if (UM_CONV_2P != 2) acc2[nt] = T::mfma(pwh[nt], bl, acc2[nt]);
+                            acc2[nt] = T::mfma(pwl[nt], bh, acc2[nt]);
+                            acc2[nt] = T::mfma(pwh[nt], bl, acc2[nt]);
                         }
                         acc2[nt] = T::mfma(pwh[nt], bh, acc2[nt]);
                     }
@@ -749,7 +734,7 @@ __global__ __launch_bounds__(512, (NSLOT == 2 && NT < 4 ? 2 : 1)) void conv_rows
                 const int sc = dcp ^ ((r >> 3) & 1);
                 const unsigned off = rowoff[k] + (unsigned)((cc * 16 + 8 * sc) * 2);
 #pragma unroll
-                for (int pl = 0; pl < NS; ++pl) conv_dma16(a.ap + pl * a.a_plane_stride, off, buf + pl * ATILE + (32 * jr) * 32);
+                for (int pl = 0; pl < NS; ++pl) um_lds_dma16(a.ap + pl * a.a_plane_stride, off, buf + pl * ATILE + (32 * jr) * 32);
             }
         } else {
             const int q = wave + 8 * (k - 2);
@@ -761,7 +746,7 @@ __global__ __launch_bounds__(512, (NSLOT == 2 && NT < 4 ? 2 : 1)) void conv_rows
                 const unsigned off = (unsigned)(((long)n * ktot + (ky * KW + kx) * a.Cin + cc * 16 + 8 * sc) * 2);
 #pragma unroll
                 for (int pl = 0; pl < NS; ++pl)
-                    conv_dma16(a.wp + pl * a.w_plane_stride, off, buf + NS * ATILE + (kx * NS + pl) * WTILE + (32 * jb) * 32);
+                    um_lds_dma16(a.wp + pl * a.w_plane_stride, off, buf + NS * ATILE + (kx * NS + pl) * WTILE + (32 * jb) * 32);
             }
         }
     };
@@ -849,8 +834,8 @@ __global__ __launch_bounds__(512, (NSLOT == 2 && NT < 4 ? 2 : 1)) void conv_rows
                 const i16x8 wh = *reinterpret_cast<const i16x8*>(wt + nt * 32 * 32 + foffw);
                 if (NS == 2) {
                     const i16x8 wl = *reinterpret_cast<const i16x8*>(wt + WTILE + nt * 32 * 32 + foffw);
-                    if (UM_CONV_2P != 1) acc[nt] = T::mfma(wl, bh, acc[nt]);
-                    if (UM_CONV_2P != 2) acc[nt] = T::mfma(wh, bl, acc[nt]);
+                    acc[nt] = T::mfma(wl, bh, acc[nt]);
+                    acc[nt] = T::mfma(wh, bl, acc[nt]);
                 }
                 acc[nt] = T::mfma(wh, bh, acc[nt]);
             }
@@ -952,7 +937,7 @@ __device__ __forceinline__ void conv_patch_body(const ConvArgs& a, unsigned char
                 const int sc = dcp ^ ((r >> 3) & 1);
                 const unsigned off = rowoff[i] + (unsigned)((cc * 16 + 8 * sc) * 2);
 #pragma unroll
-                for (int pl = 0; pl < NS; ++pl) conv_dma16(a.ap + pl * a.a_plane_stride, off, buf + pl * ATILE + (32 * blk) * 32);
+                for (int pl = 0; pl < NS; ++pl) um_lds_dma16(a.ap + pl * a.a_plane_stride, off, buf + pl * ATILE + (32 * blk) * 32);
             }
     };
     // ---- on-load path: item i of chunk cc = the 8 channels cc * 16 + 8 * nsc of patch pixel 32 (wave + 8 i) + (lane >> 1)
@@ -1006,7 +991,7 @@ __device__ __forceinline__ void conv_patch_body(const ConvArgs& a, unsigned char
                 const unsigned off = (unsigned)(((long)n * ktot + (ky * 3 + kx) * a.Cin + cc * 16 + 8 * sc) * 2);
 #pragma unroll
                 for (int pl = 0; pl < NS; ++pl)
-                    conv_dma16(a.wp + pl * a.w_plane_stride, off, buf + (kx * NS + pl) * WTILE + (32 * jb) * 32);
+                    um_lds_dma16(a.wp + pl * a.w_plane_stride, off, buf + (kx * NS + pl) * WTILE + (32 * jb) * 32);
             }
         }
     };
@@ -1075,8 +1060,8 @@ __device__ __forceinline__ void conv_patch_body(const ConvArgs& a, unsigned char
                     const i16x8 wh = *reinterpret_cast<const i16x8*>(wt + nt * 32 * 32 + foffw);
                     if (NS == 2) {
                         const i16x8 wl = *reinterpret_cast<const i16x8*>(wt + WTILE + nt * 32 * 32 + foffw);
-                        if (UM_CONV_2P != 1) acc[nt] = T::mfma(wl, bh, acc[nt]);
-                        if (UM_CONV_2P != 2) acc[nt] = T::mfma(wh, bl, acc[nt]);
+                        acc[nt] = T::mfma(wl, bh, acc[nt]);
+                        acc[nt] = T::mfma(wh, bl, acc[nt]);
                     }
                     acc[nt] = T::mfma(wh, bh, acc[nt]);
                 }

@@ -25,11 +25,6 @@
 // fp32 accumulation (exact mode); bf16, one product (fast mode).  Weights are pre-scaled by 2^wshift.
 #include <type_traits>
 #include <stdlib.h>
-// -DUM_FFN_H1=1 (diagnostic builds: profiles/r03_precision_budget.txt): the second GEMM with gelu(H) in ONE fp16 plane
-// (W2_lo.H + W2_hi.H: 2 products instead of 3, no lo split of the hidden activations).
-#ifndef UM_FFN_H1
-#define UM_FFN_H1 0
-#endif
 #include "common.h"
 #include "planes.h"
 
@@ -75,69 +70,15 @@ struct FfnArgs {
     unsigned* range_flag;         // um_range_flags (as Kv4Args)
 };
 
-// the same with the LDS destination as an ADDRESS (an SGPR value): a flat pointer into the LDS array costs an address-space cast
-// with its null check (s_add_u32 / s_addc_u32 / s_cmp_lg_u64 / s_cselect_b32) per statement; base address + constant costs one s_add
-__device__ __forceinline__ void ffn_dma16_at(const void* base, unsigned byte_off, unsigned lds_addr) {
-    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);         // (uniform already; folds away when the compiler can prove it)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(byte_off), "s"(base), "s"(lds_addr)
-                 : "memory");
-}
-__device__ __forceinline__ void ffn_dma16(const void* base, unsigned byte_off, const unsigned char* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane(
-        (unsigned)(unsigned long)(const __attribute__((address_space(3))) unsigned char*)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(byte_off), "s"(base), "s"(dst)
-                 : "memory");
-}
-
-// Main-loop order (round 4).  1: phase A of slice i+1 FIRST, then phase B of slice i-1; the LDS-DMA statements of the next weight
-// slices ride in the gaps of the phase-A MFMAs instead of standing between the barrier and the first MFMA, the exchange read is
-// issued right behind the barrier, and the accumulator hand-over (add, send) happens in the gaps of phase B -- so the stretch of a
-// slice in which BOTH waves of a SIMD (they run in lockstep: one workgroup barrier per slice) leave the matrix pipe idle shrinks
-// from [tail + barrier + DMA issue + exchange + first fragments] to [barrier + first fragments].  0: the round-1..3 order (B then
-// A, DMA right after the barrier, hand-over after the stream).  Same arithmetic in the same order per accumulator: bitwise equal.
-#ifndef UM_FFN_ORDER
-#define UM_FFN_ORDER 1
-#endif
-// Issue priority of the pair's two waves inside the MFMA stream (UM_FFN_ORDER 1).  The partners w and w + 4 share a SIMD and run
+// Issue priority of the pair's two waves inside the MFMA stream.  The partners w and w + 4 share a SIMD and run
 // in lockstep (one workgroup barrier per slice); with equal priority the arbiter serves the OLDER wave (role 0) first, its stream
 // ends ~750 cycles before the partner's (section stamps: 2210 against 2980 cycles per slice), it idles at the barrier and the
 // partner finishes alone with the matrix pipe half used.  1: role 0 favoured in the first half of the stream, role 1 in the second;
 // 2 / 4 / 5: the favoured role alternates every 6 / 3 / 12 MFMAs; 3: role 1 favoured throughout (control); 0: equal priority
-// (rounds 1-3).
+// (rounds 1-3).  Measured and dropped; the switch is still here only because taking the constant-false `prio`
+// lambda out of `iteration` changes the register assignment of two instantiations (profiles/switch_retirement.txt).
 #ifndef UM_FFN_PRIO
 #define UM_FFN_PRIO 0
-#endif
-// Who requests the weight slices (UM_FFN_ORDER 1).  0: every wave its sixth of the slice (6 LDS-DMA statements per wave and slice).
-// 1: the ROLE-0 waves request everything (12 statements each), the role-1 waves none: role 0 is the older wave of its SIMD, the
-// arbiter serves it first and it finishes its stream ~750 cycles before its partner (section stamps) -- the requests cost issue
-// slots, not matrix-pipe time, so moving them to the wave that has the slack shortens the partner's stream, which is the one the
-// slice waits for.
-#ifndef UM_FFN_DMA_ASYM
-#define UM_FFN_DMA_ASYM 0
-#endif
-// Diagnostic builds: -DUM_FFN_NT=1 non-temporal loads of the token rows (x | y, residual), 2: ... and non-temporal stores of the output --
-// whether keeping the streamed rows out of the XCD's L2 saves the weight slices' re-fetches (profiles/r05_ffn_overfetch.txt)
-#ifndef UM_FFN_NT
-#define UM_FFN_NT 0
-#endif
-#if UM_FFN_NT >= 1
-#define UM_FFN_LD(p) __builtin_nontemporal_load(p)
-#else
-#define UM_FFN_LD(p) (*(p))
-#endif
-#if UM_FFN_NT >= 2
-#define UM_FFN_ST(p, v) __builtin_nontemporal_store(v, p)
-#else
-#define UM_FFN_ST(p, v) (*(p) = (v))
-#endif
-#ifndef UM_FFN_ROWSTORE
-#define UM_FFN_ROWSTORE 1
 #endif
 #ifndef UM_FFN_ABL
 #define UM_FFN_ABL 0     // timing ablations (results are wrong when non-zero): 1 gelu, 2 dma, 4 phase A, 8 phase B, 16 exchange, 32 residual read
@@ -248,7 +189,7 @@ __device__ __forceinline__ void kv4_project(unsigned char* ring, unsigned char* 
             const unsigned off = (unsigned)((((long)(32 * c + r)) * 256 + 8 * cc) * 2);
 #pragma unroll
             for (int pl = 0; pl < NS; ++pl)
-                ffn_dma16(k.w + pl * k.w_plane_stride, off, ring + slot * L::W1S + pl * L::W1P + blk * 1024);
+                um_lds_dma16(k.w + pl * k.w_plane_stride, off, ring + slot * L::W1S + pl * L::W1P + blk * 1024);
         }
     };
     unsigned char* myscr = scr + wave * Kv4Lds<NS>::SCRW;
@@ -400,16 +341,8 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
             const unsigned off = (unsigned)((((long)(32 * (sbase + j) + r)) * 256 + 8 * c) * 2);
 #pragma unroll
             for (int pl = 0; pl < NS; ++pl)
-                ffn_dma16(a.w1 + pl * a.w1_plane_stride, off, lds + L::W1_OFF + slot * L::W1S + pl * L::W1P + blk * 1024);
+                um_lds_dma16(a.w1 + pl * a.w1_plane_stride, off, lds + L::W1_OFF + slot * L::W1S + pl * L::W1P + blk * 1024);
         }
-    };
-    // W2 slice: rows of 64 B (4 chunks), chunk c of row r at c ^ ((r >> 2) & 3); one instruction moves 16 rows.
-    auto dma_w2 = [&](int j, int slot) {
-        const int r = 16 * wave + (lane >> 2), c = (lane & 3) ^ ((r >> 2) & 3);
-        const unsigned off = (unsigned)((((long)r) * a.hid + 32 * (sbase + j) + 8 * c) * 2);
-#pragma unroll
-        for (int pl = 0; pl < NS; ++pl)
-            ffn_dma16(a.w2 + pl * a.w2_plane_stride, off, lds + L::W2_OFF + slot * L::W2S + pl * L::W2P + wave * 1024);
     };
 
 #ifdef UM_FFN_TRACE
@@ -417,10 +350,11 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
     unsigned long long* trace_buf = g_um_ffn_trace + ((size_t)(blockIdx.x / 37) * 2 + role) * (24 * 8 + 8);
     if (tracing) trace_buf[24 * 8] = __builtin_amdgcn_s_memtime();
 #endif
-    // the same six statements one at a time (UM_FFN_ORDER 1: they are issued in the gaps of the phase-A MFMAs)
+    // The main loop requests a slice one statement at a time, in the gaps of the phase-A MFMAs: per wave the W1 slice's four
+    // statements (as dma_w1) and two of the W2 slice (rows of 64 B = 4 chunks, chunk c of row r at c ^ ((r >> 2) & 3); one
+    // instruction moves 16 rows).
     // (LDS destinations as addresses: base of the array + this wave's kilobyte, in an SGPR, + a compile-time constant)
-    const unsigned lds_wave = __builtin_amdgcn_readfirstlane(
-        (unsigned)(unsigned long)(const __attribute__((address_space(3))) unsigned char*)lds) + (unsigned)wave * 1024u;
+    const unsigned lds_wave = um_lds_addr(lds) + (unsigned)wave * 1024u;
     auto dma_piece = [&](int k, int jw1, int jw2, int slot) {      // k = 0..3: W1 (i = k >> 1, plane k & 1), 4..5: W2 plane k - 4
         if (k < 4) {
             const int i = k >> 1, pl = k & 1;
@@ -428,31 +362,13 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
             const int blk = 8 * i + wave;
             const int r = 2 * blk + half, c = tl ^ r;
             const unsigned off = (unsigned)((((long)(32 * (sbase + jw1) + r)) * 256 + 8 * c) * 2);
-            ffn_dma16_at(a.w1 + pl * a.w1_plane_stride, off, lds_wave + (unsigned)(L::W1_OFF + slot * L::W1S + pl * L::W1P + 8 * i * 1024));
+            um_lds_dma16_at(a.w1 + pl * a.w1_plane_stride, off, lds_wave + (unsigned)(L::W1_OFF + slot * L::W1S + pl * L::W1P + 8 * i * 1024));
         } else {
             const int pl = k - 4;
             if (pl >= NS) return;
             const int r = 16 * wave + (lane >> 2), c = (lane & 3) ^ ((r >> 2) & 3);
             const unsigned off = (unsigned)((((long)r) * a.hid + 32 * (sbase + jw2) + 8 * c) * 2);
-            ffn_dma16_at(a.w2 + pl * a.w2_plane_stride, off, lds_wave + (unsigned)(L::W2_OFF + slot * L::W2S + pl * L::W2P));
-        }
-    };
-
-    // UM_FFN_DMA_ASYM: the role-0 wave of pair p requests a quarter of the slice: k = 0..7: W1 rows 2 (4 (k >> 1) + p) + half, plane
-    // k & 1;  k = 8..11: W2 rows 16 (2 p + ((k - 8) >> 1)) + lane / 4, plane k & 1
-    auto dma_piece_asym = [&](int k, int jw1, int jw2, int slot) {
-        const int pl = k & 1;
-        if (pl >= NS) return;
-        if (k < 8) {
-            const int blk = 4 * (k >> 1) + pair;
-            const int r = 2 * blk + half, c = tl ^ r;
-            const unsigned off = (unsigned)((((long)(32 * (sbase + jw1) + r)) * 256 + 8 * c) * 2);
-            ffn_dma16(a.w1 + pl * a.w1_plane_stride, off, lds + L::W1_OFF + slot * L::W1S + pl * L::W1P + blk * 1024);
-        } else {
-            const int blk = 2 * pair + ((k - 8) >> 1);
-            const int r = 16 * blk + (lane >> 2), c = (lane & 3) ^ ((r >> 2) & 3);
-            const unsigned off = (unsigned)((((long)r) * a.hid + 32 * (sbase + jw2) + 8 * c) * 2);
-            ffn_dma16(a.w2 + pl * a.w2_plane_stride, off, lds + L::W2_OFF + slot * L::W2S + pl * L::W2P + blk * 1024);
+            um_lds_dma16_at(a.w2 + pl * a.w2_plane_stride, off, lds_wave + (unsigned)(L::W2_OFF + slot * L::W2S + pl * L::W2P));
         }
     };
 
@@ -465,8 +381,8 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
         float xmx = 0.f;
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
-            const f32x4 v0 = UM_FFN_LD(reinterpret_cast<const f32x4*>(src + 16 * ks));
-            const f32x4 v1 = UM_FFN_LD(reinterpret_cast<const f32x4*>(src + 16 * ks + 4));
+            const f32x4 v0 = *reinterpret_cast<const f32x4*>(src + 16 * ks);
+            const f32x4 v1 = *reinterpret_cast<const f32x4*>(src + 16 * ks + 4);
 #pragma unroll
             for (int j = 0; j < 4; ++j) xmx = fmaxf(xmx, fmaxf(__builtin_fabsf(v0[j]), __builtin_fabsf(v1[j])));
             const u32x4 h = {T::pack2(v0[0], v0[1]), T::pack2(v0[2], v0[3]), T::pack2(v1[0], v1[1]), T::pack2(v1[2], v1[3])};
@@ -570,13 +486,13 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
             }
             break;
         case 1:                                  // lo plane: 2 x (v_fma_mixlo_f16 + v_fma_mixhi_f16) per stage (Fp16::lo2)
-            if (NS == 2 && !UM_FFN_H1) {
+            if (NS == 2) {
 #pragma unroll
                 for (int q = 0; q < 2; ++q) f.wl[q] = T::lo2(g[q].x[0], g[q].x[1], f.wh[q], neg1);
             }
             break;
         case 2:
-            if (NS == 2 && !UM_FFN_H1) {
+            if (NS == 2) {
 #pragma unroll
                 for (int q = 2; q < 4; ++q) f.wl[q] = T::lo2(g[q].x[0], g[q].x[1], f.wh[q], neg1);
             }
@@ -586,7 +502,7 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
             const auto sy = __builtin_amdgcn_permlane32_swap(f.wh[1], f.wh[3], false, false);
             const u32x4 fh = {sx[0], sy[0], sx[1], sy[1]};
             pf[0] = __builtin_bit_cast(i16x8, fh);
-            if (NS == 2 && !UM_FFN_H1) {
+            if (NS == 2) {
                 const auto tx = __builtin_amdgcn_permlane32_swap(f.wl[0], f.wl[2], false, false);
                 const auto ty = __builtin_amdgcn_permlane32_swap(f.wl[1], f.wl[3], false, false);
                 const u32x4 fl = {tx[0], ty[0], tx[1], ty[1]};
@@ -597,143 +513,24 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
         }
     };
 
-    // One iteration i (after barrier i):
-    //     MFMA pipe :  phase B of slice i-1 (12 MFMAs, fragments built last iteration)  then  phase A of slice i+1 (24)
-    //     VALU      :  GELU of slice i (4 x 4 stages) and its H^T fragments (4 stages), pinned behind those MFMAs
-    // hipcc does not interleave the two on its own (and gives up on a sched_group_barrier pipeline of this size), so the
-    // order is written out: every MFMA is followed by its share of stages and a scheduling fence.
     i16x8 pf[NS];                   // H^T fragments of the previous slice
-    auto iteration = [&](auto has_a_tag, auto has_b_tag, int i) {
-        constexpr bool HAS_A = decltype(has_a_tag)::value && !(UM_FFN_ABL & 4);
-        constexpr bool HAS_B = decltype(has_b_tag)::value && !(UM_FFN_ABL & 8);
-        constexpr int MF = (NS == 2) ? 3 : 1;
-        constexpr int MFB = (NS == 2 && UM_FFN_H1) ? 2 : MF;       // products of phase B (see UM_FFN_H1)
-        constexpr int NMFMA = (HAS_A ? 8 * MF : 0) + (HAS_B ? 4 * MFB : 0);
-        constexpr int NGELU = 4 * UM_GELU_STAGES, NSTAGE = NGELU + 4;
-        const int slot = i & 1;
-        const unsigned char* w1s = lds + L::W1_OFF + (slot ^ 1) * L::W1S;     // W1(i+1)
-        const unsigned char* w2s = lds + (slot ^ 1) * L::W2S;                 // (+ W2_OFF inside boff)     // W2(i-1)
-        UM_FSTAMP(0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // W1(i+1), W2(i-1): this thread's pieces have landed
-        UM_FSTAMP(1);
-        __syncthreads();
-        UM_FSTAMP(2);
-        if (!(UM_FFN_ABL & 2)) {
-            if (i + 2 < nslice) dma_w1(i + 2, slot);
-            dma_w2(i, slot);
-        }
-        f32x4 r0 = {0.f, 0.f, 0.f, 0.f}, r1 = r0;
-        if (!(UM_FFN_ABL & 16)) {
-            const unsigned char* p = xb_in + slot * (8 * L::XB);
-            r0 = *reinterpret_cast<const f32x4*>(p);
-            r1 = *reinterpret_cast<const f32x4*>(p + 1024);
-        }
-        Gelu2 g[4];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                g[q].x[i] = (sc[2 * q + i] + r0[2 * q + i]) * a.out_scale;
-                g[2 + q].x[i] = (sc[4 + 2 * q + i] + r1[2 * q + i]) * a.out_scale;
-            }
-        }
-        Frag fr;
-        i16x8 pfn[NS];
-        int done = 0;                                              // VALU stages issued so far (compile-time after unrolling)
-        auto valu_share = [&](int slot_idx) {                      // stages [slot_idx, slot_idx + 1) * NSTAGE / NMFMA
-            const int upto = (slot_idx + 1) * NSTAGE / (NMFMA > 0 ? NMFMA : 1);
-            for (; done < upto; ++done) {
-                if (done < NGELU) ffn_gelu_stage(g[done / UM_GELU_STAGES], done % UM_GELU_STAGES);
-                else frag_stage(fr, g, pfn, done - NGELU);
-            }
-        };
-        f32x16 scn, scm;                                           // phase A alternates two accumulators (see phase B)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) scn[r] = scm[r] = 0.f;
-        UM_FSTAMP(3);
-        __builtin_amdgcn_s_setprio(1);
-        int mslot = 0;
-        i16x8 fh[3], fl[3];                                        // phase A fragments, two k-steps ahead of their MFMAs
-        if (HAS_A) {
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                fh[ks] = *reinterpret_cast<const i16x8*>(w1s + aoff[ks]);
-                if (NS == 2) fl[ks] = *reinterpret_cast<const i16x8*>(w1s + L::W1P + aoff[ks]);
-            }
-        }
-        if (HAS_B) {
-            // product index outer, output tile inner: consecutive MFMAs write different accumulators (a filler between two
-            // MFMAs on the same accumulator costs the forwarding path, ~43 cycles -- MI355X_MICROARCH.md)
-            i16x8 vh[4], vl[4];
-#pragma unroll
-            for (int ot = 0; ot < 4; ++ot) {
-                vh[ot] = *reinterpret_cast<const i16x8*>(w2s + boff[ot]);
-                if (NS == 2) vl[ot] = *reinterpret_cast<const i16x8*>(w2s + L::W2P + boff[ot]);
-            }
-#pragma unroll
-            for (int m = 0; m < MFB; ++m)
-#pragma unroll
-                for (int ot = 0; ot < 4; ++ot) {
-                    const i16x8 wa = (NS == 2 && m == 0) ? vl[ot] : vh[ot];
-                    const i16x8 hb = (NS == 2 && MFB == 3 && m == 1) ? pf[NS - 1] : pf[0];
-                    o[ot] = T::mfma(wa, hb, o[ot]);
-                    valu_share(mslot++);
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-                    __builtin_amdgcn_sched_group_barrier(0x402, 16, 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-        }
-        if (HAS_A) {
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                if (ks + 2 < 8) {
-                    fh[(ks + 2) % 3] = *reinterpret_cast<const i16x8*>(w1s + aoff[ks + 2]);
-                    if (NS == 2) fl[(ks + 2) % 3] = *reinterpret_cast<const i16x8*>(w1s + L::W1P + aoff[ks + 2]);
-                }
-#pragma unroll
-                for (int m = 0; m < MF; ++m) {
-                    const i16x8 wa = (NS == 2 && m == 0) ? fl[ks % 3] : fh[ks % 3];
-                    const i16x8 xb = (NS == 2 && m == 1) ? xf[NS - 1][ks] : xf[0][ks];
-                    if ((ks * MF + m) & 1) scm = T::mfma(wa, xb, scm);
-                    else scn = T::mfma(wa, xb, scn);
-                    valu_share(mslot++);
-                    if (m == 0 && ks + 2 < 8) __builtin_amdgcn_sched_group_barrier(0x100, NS, 1);
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-                    __builtin_amdgcn_sched_group_barrier(0x402, 16, 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-        __builtin_amdgcn_s_setprio(0);
-        UM_FSTAMP(4);
-        for (; done < NSTAGE; ++done) {                            // whatever no MFMA was left to hide
-            if (done < NGELU) ffn_gelu_stage(g[done / UM_GELU_STAGES], done % UM_GELU_STAGES);
-            else frag_stage(fr, g, pfn, done - NGELU);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (decltype(has_a_tag)::value) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) scn[r] += scm[r];
-            send(scn, slot ^ 1);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) sc[r] = scn[r];
-        }
-#pragma unroll
-        for (int pl = 0; pl < NS; ++pl) pf[pl] = pfn[pl];
-        UM_FSTAMP(5);
-    };
-
-    // ---- UM_FFN_ORDER 1: one iteration i (after barrier i) --------------------------------------------------------------------
+    // ---- one iteration i (after barrier i) ------------------------------------------------------------------------------------
     //     MFMA pipe :  phase A of slice i+1 (24 MFMAs)  then  phase B of slice i-1 (12, fragments built last iteration)
-    //     gaps      :  GELU of slice i + its H^T fragments (as before, one share per MFMA); the LDS-DMA statements of W1(i+2) and
-    //                  W2(i) behind the first phase-A MFMAs; the accumulator hand-over (add, send) behind the first phase-B MFMAs
-    auto iteration1 = [&](auto has_a_tag, auto has_b_tag, auto dma1_tag, auto slot_tag, int i) {
+    //     gaps      :  GELU of slice i (4 x 4 stages) + its H^T fragments (4 stages), one share per MFMA; the LDS-DMA statements of
+    //                  W1(i+2) and W2(i) behind the first phase-A MFMAs; the accumulator hand-over (add, send) behind the first
+    //                  phase-B MFMAs
+    // Phase A of slice i+1 FIRST, then phase B of slice i-1: the DMA statements ride in the gaps of the phase-A MFMAs instead of
+    // standing between the barrier and the first MFMA, and the exchange read is issued right behind the barrier -- so the stretch of
+    // a slice in which BOTH waves of a SIMD (they run in lockstep: one workgroup barrier per slice) leave the matrix pipe idle is
+    // [barrier + first fragments] only.
+    // hipcc does not interleave the VALU stages with the MFMAs on its own (and gives up on a sched_group_barrier pipeline of this
+    // size), so the order is written out: every MFMA is followed by its share of stages and a scheduling fence.
+    auto iteration = [&](auto has_a_tag, auto has_b_tag, auto dma1_tag, auto slot_tag, int i) {
         constexpr bool HAS_A = decltype(has_a_tag)::value && !(UM_FFN_ABL & 4);
         constexpr bool HAS_B = decltype(has_b_tag)::value && !(UM_FFN_ABL & 8);
         constexpr bool DMA1 = decltype(dma1_tag)::value;           // W1(i+2) exists
         constexpr int MF = (NS == 2) ? 3 : 1;
-        constexpr int MFB = (NS == 2 && UM_FFN_H1) ? 2 : MF;
-        constexpr int NA = HAS_A ? 8 * MF : 0, NB = HAS_B ? 4 * MFB : 0, NMFMA = NA + NB;
+        constexpr int NA = HAS_A ? 8 * MF : 0, NB = HAS_B ? 4 * MF : 0, NMFMA = NA + NB;
         constexpr int NGELU = 4 * UM_GELU_STAGES, NSTAGE = NGELU + 4;
         // ring slot = i & 1, at COMPILE time (round 5: the loop runs two slices per trip): every fragment read, exchange access and
         // LDS-DMA destination of the slice is register + immediate -- with the slot in a register the slice carried 16 v_add_u32 and
@@ -781,19 +578,14 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
         };
         // LDS-DMA pieces still to issue: W1(i+2) (4 statements at NS = 2) when it exists, W2(i) (2 statements); one per MFMA gap
         // from gap 1 on (gap 0 carries the exchange arithmetic)
-        int piece = UM_FFN_DMA_ASYM ? (DMA1 ? 0 : 8) : (DMA1 ? 0 : 4);
-        constexpr int NPIECE = UM_FFN_DMA_ASYM ? 12 : 6;
+        int piece = DMA1 ? 0 : 4;
+        constexpr int NPIECE = 6;
         auto dma_share = [&](int slot_idx) {
             if (UM_FFN_ABL & 2) return;
             if (slot_idx >= 1 && piece < NPIECE) {
-                if (UM_FFN_DMA_ASYM) {
-                    if (role == 0) dma_piece_asym(piece, i + 2, i, slot);
-                    piece += (NS == 1) ? 2 : 1;                            // (one plane: the odd pieces do not exist)
-                } else {
-                    dma_piece(piece, i + 2, i, slot);
-                    ++piece;
-                    if (NS == 1 && (piece == 1 || piece == 3)) ++piece;    // (one plane: pieces 1, 3, 5 do not exist)
-                }
+                dma_piece(piece, i + 2, i, slot);
+                ++piece;
+                if (NS == 1 && (piece == 1 || piece == 3)) ++piece;        // (one plane: pieces 1, 3, 5 do not exist)
             }
         };
         f32x16 scn, scm;
@@ -852,11 +644,11 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
                 }
             }
 #pragma unroll
-            for (int m = 0; m < MFB; ++m)
+            for (int m = 0; m < MF; ++m)
 #pragma unroll
                 for (int ot = 0; ot < 4; ++ot) {
                     const i16x8 wa = (NS == 2 && m == 0) ? vl[ot] : vh[ot];
-                    const i16x8 hb = (NS == 2 && MFB == 3 && m == 1) ? pf[NS - 1] : pf[0];
+                    const i16x8 hb = (NS == 2 && m == 1) ? pf[NS - 1] : pf[0];
                     prio(mslot);
                     o[ot] = T::mfma(wa, hb, o[ot]);
                     const int bslot = m * 4 + ot;
@@ -890,14 +682,9 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
         }
         if (!(UM_FFN_ABL & 2)) {
             while (piece < NPIECE) {                               // pieces no gap took (short streams: one plane, ablation builds)
-                if (UM_FFN_DMA_ASYM) {
-                    if (role == 0) dma_piece_asym(piece, i + 2, i, slot);
-                    piece += (NS == 1) ? 2 : 1;
-                } else {
-                    dma_piece(piece, i + 2, i, slot);
-                    ++piece;
-                    if (NS == 1 && (piece == 1 || piece == 3)) ++piece;
-                }
+                dma_piece(piece, i + 2, i, slot);
+                ++piece;
+                if (NS == 1 && (piece == 1 || piece == 3)) ++piece;
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -915,33 +702,29 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
         UM_FSTAMP(5);
     };
 
-    if (UM_FFN_ORDER == 1) {
+    {
         using Y = std::true_type;
         using N = std::false_type;
         using S0 = std::integral_constant<int, 0>;
         using S1 = std::integral_constant<int, 1>;
         if ((nslice & 1) == 0 && nslice >= 4) {                    // every shipped geometry: hid = 1024 -> 32 / 16 / 8 slices
-            iteration1(Y{}, N{}, Y{}, S0{}, 0);
+            iteration(Y{}, N{}, Y{}, S0{}, 0);
             int i = 1;
             for (; i + 4 < nslice; i += 2) {                       // slices 1 .. nslice - 4 in pairs (odd, even)
-                iteration1(Y{}, Y{}, Y{}, S1{}, i);
-                iteration1(Y{}, Y{}, Y{}, S0{}, i + 1);
+                iteration(Y{}, Y{}, Y{}, S1{}, i);
+                iteration(Y{}, Y{}, Y{}, S0{}, i + 1);
             }
-            iteration1(Y{}, Y{}, Y{}, S1{}, nslice - 3);
-            iteration1(Y{}, Y{}, N{}, S0{}, nslice - 2);
-            iteration1(N{}, Y{}, N{}, S1{}, nslice - 1);
+            iteration(Y{}, Y{}, Y{}, S1{}, nslice - 3);
+            iteration(Y{}, Y{}, N{}, S0{}, nslice - 2);
+            iteration(N{}, Y{}, N{}, S1{}, nslice - 1);
         } else {                                                    // any other slice count: the slot in a register
-            if (2 < nslice) iteration1(Y{}, N{}, Y{}, 0, 0);
-            else iteration1(Y{}, N{}, N{}, 0, 0);
+            if (2 < nslice) iteration(Y{}, N{}, Y{}, 0, 0);
+            else iteration(Y{}, N{}, N{}, 0, 0);
             int i = 1;
-            for (; i + 2 < nslice; ++i) iteration1(Y{}, Y{}, Y{}, i & 1, i);
-            for (; i + 1 < nslice; ++i) iteration1(Y{}, Y{}, N{}, i & 1, i);
-            iteration1(N{}, Y{}, N{}, (nslice - 1) & 1, nslice - 1);
+            for (; i + 2 < nslice; ++i) iteration(Y{}, Y{}, Y{}, i & 1, i);
+            for (; i + 1 < nslice; ++i) iteration(Y{}, Y{}, N{}, i & 1, i);
+            iteration(N{}, Y{}, N{}, (nslice - 1) & 1, nslice - 1);
         }
-    } else {
-        iteration(std::true_type{}, std::false_type{}, 0);
-        for (int i = 1; i + 1 < nslice; ++i) iteration(std::true_type{}, std::true_type{}, i);
-        iteration(std::false_type{}, std::true_type{}, nslice - 1);
     }
     // The residual rows (this lane's 64 fp32 values of x) are requested HERE, a whole exchange + LayerNorm ahead of their use: the token
     // operand's 64 registers are dead since the last phase A.  (They are a second read of x: 50 MB of the launch's 182 MB of fabric reads
@@ -955,7 +738,7 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
             const float* res = a.x + (long)min(tok, a.M - 1) * 128 + 4 * half;
 #pragma unroll
             for (int q = 0; q < 16; ++q)
-                rr[q] = (UM_FFN_ABL & 32) ? f32x4{0.f, 0.f, 0.f, 0.f} : UM_FFN_LD(reinterpret_cast<const f32x4*>(res + 8 * q));
+                rr[q] = (UM_FFN_ABL & 32) ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(res + 8 * q);
         }
         if (!(UM_FFN_ABL & 8)) {
 #pragma unroll
@@ -964,7 +747,7 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
                 if (NS == 2) {
                     const i16x8 vl = *reinterpret_cast<const i16x8*>(w2s + L::W2P + boff[ot]);
                     o[ot] = T::mfma(vl, pf[0], o[ot]);
-                    if (!UM_FFN_H1) o[ot] = T::mfma(vh, pf[NS - 1], o[ot]);
+                    o[ot] = T::mfma(vh, pf[NS - 1], o[ot]);
                 }
                 o[ot] = T::mfma(vh, pf[0], o[ot]);
             }
@@ -988,7 +771,7 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
             const unsigned off = (unsigned)((((long)r) * 256 + 8 * cc) * 2);
 #pragma unroll
             for (int pl = 0; pl < NS; ++pl)
-                ffn_dma16(a.kv.w + pl * a.kv.w_plane_stride, off, lds + pl * L::W1P + blk * 1024);
+                um_lds_dma16(a.kv.w + pl * a.kv.w_plane_stride, off, lds + pl * L::W1P + blk * 1024);
         }
     }
     unsigned char* ob = lds + (KV4 ? 65536 : 0) + pair * 16384 + lane * 16;
@@ -1072,7 +855,6 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
         }
     half_wave_pair(s2, u, v2);
     const float rstd = 1.0f / sqrtf((u + v2) * (1.0f / 128.0f) + a.eps);
-#if UM_FFN_ROWSTORE
     if (role == 0) {
         // lane holds, for its token, features 32 ot + 8 g + 4 half + i  (reg 4 g + i of tile ot).  The tile leaves through LDS as
         // WHOLE ROWS (round 5): a store instruction of the row-per-lane form touches 32 separate 32-byte pieces, and the tail of 16 of
@@ -1103,32 +885,9 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
             const int r = 2 * j + half;
             const f32x4 v = *reinterpret_cast<const f32x4*>(stg + r * 512 + ((cc ^ r) << 4));
             const int trow = m0 + 32 * pair + r;
-            if (trow < a.M) UM_FFN_ST(reinterpret_cast<f32x4*>(a.out + (long)trow * 128 + 4 * cc), v);
+            if (trow < a.M) *reinterpret_cast<f32x4*>(a.out + (long)trow * 128 + 4 * cc) = v;
         }
     }
-#else       // round 1-4: every lane stores its own token's 16-byte pieces (diagnostic builds: -DUM_FFN_ROWSTORE=0)
-    if (KV4 ? role == 0 : tok < a.M) {
-        // lane holds, for its token, features 32 ot + 8 g + 4 half + i  (reg 4 g + i of tile ot)
-        const int tokc = min(tok, a.M - 1);                         // (KV4: rows past M are computed on a valid row and never stored)
-        float* dst = a.out + (long)tokc * 128 + 4 * half;
-#pragma unroll
-        for (int ot = 0; ot < 4; ++ot)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int n = 32 * ot + 8 * g;
-                const f32x4 gm = *reinterpret_cast<const f32x4*>(a.gamma + n + 4 * half);
-                const f32x4 bt = *reinterpret_cast<const f32x4*>(a.beta + n + 4 * half);
-                f32x4 yv;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) yv[i] = (o[ot][4 * g + i] - mean) * rstd * gm[i] + bt[i] + rr[4 * ot + g][i];
-                if (tok < a.M) UM_FFN_ST(reinterpret_cast<f32x4*>(dst + n), yv);
-                if constexpr (KV4) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) o[ot][4 * g + i] = yv[i];
-                }
-            }
-    }
-#endif
 #ifdef UM_FFN_TRACE
     if (tracing) trace_buf[24 * 8 + 2] = __builtin_amdgcn_s_memtime();          // end of LayerNorm + residual + stores
 #endif

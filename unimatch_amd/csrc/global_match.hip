@@ -43,27 +43,6 @@ struct GsvArgs {
     int nbatch, qtiles, chunk;
 };
 
-// 16 (or 4) bytes per lane, global -> LDS without passing through VGPRs (LDS address = wave-uniform dst + size * lane).
-// Issued through inline asm: hipcc would otherwise drain the transfer in front of the next LDS read (see window_attn.hip).
-__device__ __forceinline__ void gsv_dma16(const void* base, unsigned byte_off, const unsigned char* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane(
-        (unsigned)(unsigned long)(const __attribute__((address_space(3))) unsigned char*)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(byte_off), "s"(base), "s"(dst)
-                 : "memory");
-}
-__device__ __forceinline__ void gsv_dma4(const void* base, unsigned byte_off, const unsigned char* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane(
-        (unsigned)(unsigned long)(const __attribute__((address_space(3))) unsigned char*)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(byte_off), "s"(base), "s"(dst)
-                 : "memory");
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // gsv3_kernel: software-pipelined at instruction level.
 //
@@ -86,9 +65,7 @@ __device__ __forceinline__ void gsv_static_for(std::integer_sequence<int, Is...>
     (f(std::integral_constant<int, Is>{}), ...);
 }
 
-#ifndef GSV3_FAST_LIMIT
-#define GSV3_FAST_LIMIT 40.f
-#endif
+constexpr float GSV3_FAST_LIMIT = 40.f;        // a tile maximum this far (powers of two) above the offset sends the tile to the slow path
 
 template <class T, int NS, int NV, bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void gsv3_kernel(GsvArgs a) {
@@ -139,13 +116,13 @@ __global__ __launch_bounds__(256, 2) void gsv3_kernel(GsvArgs a) {
         if constexpr (NS == 2 && NV == 2 && !CAUSAL) asm volatile("" : "+v"(row));
         const int key = min(t * TK + row, a.Lk - 1);
         const unsigned off = kbase_bytes + (unsigned)key * (UM_CHANNELS * 2) + ((scp ^ (row & 15)) << 4);
-        gsv_dma16(a.kp + pl * a.k_plane_stride, off, slot + pl * PLANE + (16 * wave + 4 * j) * 256);
+        um_lds_dma16(a.kp + pl * a.k_plane_stride, off, slot + pl * PLANE + (16 * wave + 4 * j) * 256);
     };
     const float* vbase = a.v + (long)b * a.v_batch_stride;
     auto v_piece = [&](int t, unsigned char* vslot) {
         if (wave < NV) {
             const int key = min(t * TK + lane, a.Lk - 1);
-            gsv_dma4(vbase + wave * a.v_chan_stride, (unsigned)key * 4, vslot + wave * TK * 4);
+            um_lds_dma4(vbase + wave * a.v_chan_stride, (unsigned)key * 4, vslot + wave * TK * 4);
         }
     };
     auto stage_all = [&](int t, int i) {          // tile with local index i -> K slot i & 1, value slot i & 3
@@ -417,10 +394,9 @@ __global__ __launch_bounds__(256, 2) void gsv3_kernel(GsvArgs a) {
 //   * a wave owns 64 queries = two 32-query blocks: one K fragment read from LDS feeds two MFMAs per product, one tile
 //     costs 96 MFMAs (exact) against 256 softmax VALU + 48 LDS reads + 9 DMA pieces: 3.6 fillers per MFMA, under the ~5 a
 //     lone wave can hide in an MFMA's 32-cycle shadow (MI355X_MICROARCH.md, "one wave per SIMD");
-//   * the Q fragments (128 registers in exact mode) live in the accumulator half of the register file: the MFMAs are issued
-//     through inline asm with the B operand constrained to AGPRs, the score accumulators stay in VGPRs where the softmax
-//     reads them.  hipcc does not see these MFMAs, so the MFMA -> VALU read distance is kept by construction: the softmax
-//     of a tile starts after the third MFMA of the NEXT iteration (plus a workgroup barrier) following the last write;
+//   * the Q fragments (128 registers in exact mode) live in the accumulator half of the register file (pinned there, see
+//     below), the score accumulators stay in VGPRs where the softmax reads them; the softmax of a tile starts after the third
+//     MFMA of the NEXT iteration (plus a workgroup barrier) following the last write;
 //   * no tile maximum on the fast path: the offset Ms only has to keep exp2() finite, so a tile is simply evaluated and
 //     the running sum checked afterwards; if it left (0, 2^90) the lane's state is restored from the pre-tile copy and the
 //     tile redone on the renormalising path (the scores are still in their registers), which also adjusts the pending
@@ -436,32 +412,9 @@ __global__ __launch_bounds__(256, 2) void gsv3_kernel(GsvArgs a) {
 // (build.py, this file only) so that the accumulators are selected in VGPRs although the function uses AGPRs.  Same instruction
 // stream as before (checked in the .s: A = VGPR fragment, B = a[..], C/D = v[..]), and the compiler inserts whatever wait states a
 // future change needs.
-#ifndef UM_GSV4_ASM_MFMA
-template <class T> struct GsvMfmaA {
-    static __device__ __forceinline__ void acc(f32x16& d, i16x8 a, i16x8 b) { d = T::mfma(a, b, d); }
-    static __device__ __forceinline__ void init(f32x16& d, i16x8 a, i16x8 b, const f32x16& c) { d = T::mfma(a, b, c); }
-};
-#else       // diagnostic builds: rounds 2-5's hand-issued form, for the same-box A/B (profiles/r06_gsv4_builtin_ab.txt)
-template <class T> struct GsvMfmaA;
-template <> struct GsvMfmaA<Fp16> {
-    static __device__ __forceinline__ void acc(f32x16& d, i16x8 a, i16x8 b) {
-        asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-    }
-    static __device__ __forceinline__ void init(f32x16& d, i16x8 a, i16x8 b, const f32x16& c) {
-        asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "a"(b), "v"(c));
-    }
-};
-template <> struct GsvMfmaA<Bf16> {
-    static __device__ __forceinline__ void acc(f32x16& d, i16x8 a, i16x8 b) {
-        asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-    }
-    static __device__ __forceinline__ void init(f32x16& d, i16x8 a, i16x8 b, const f32x16& c) {
-        asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "a"(b), "v"(c));
-    }
-};
-#endif
 
-// LDS-DMA with the destination formed in M0 by the same statement (s_add of a wave-uniform base and an immediate).  M0 is DECLARED
+// This kernel's own LDS-DMA form (the shared one: um_lds_dma16, common.h), with the destination formed in M0 by the same statement
+// (s_add of a wave-uniform base and an immediate) and nothing saved or restored: one scalar instruction per piece.  M0 is DECLARED
 // clobbered (round 6; hipcc honours it -- it re-materialises M0 for its own users behind the statement -- and warns that M0 is a
 // reserved register: -Wno-inline-asm in build.py); rounds 2-5 relied on "hipcc keeps nothing in M0 in this kernel".
 template <int IMM>
@@ -470,9 +423,6 @@ __device__ __forceinline__ void gsv4_dma16(const void* base, unsigned byte_off, 
 }
 __device__ __forceinline__ void gsv4_dma4(const void* base, unsigned byte_off, unsigned lds_dst) {
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" : : "v"(byte_off), "s"(base), "s"(lds_dst) : "memory", "m0");
-}
-__device__ __forceinline__ unsigned gsv4_lds_addr(const unsigned char* p) {
-    return __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(const __attribute__((address_space(3))) unsigned char*)p);
 }
 
 struct GsvAcc4 {
@@ -497,13 +447,8 @@ __global__ __launch_bounds__(256, 1) void gsv4_kernel(GsvArgs a) {
     // relative to, l, acc -- [field][thread], conflict free, touched by the owning lane only: no synchronisation) and restarts
     // level 1 from zero: chains of 256 + 12 instead of 3072, no extra live register in the pinned blocks.
     constexpr int L2OFF = DUMP + 256;
-#ifdef UM_GSV4_ONE_LEVEL        // diagnostic builds: the single chain of rounds 2-5 (same-box A/B of what the flushes cost)
-    constexpr int FLUSH = 1 << 30;
-#else
     constexpr int FLUSH = 8;
-#endif
     __shared__ __attribute__((aligned(16))) unsigned char lds[L2OFF + 8 * 256 * 4];   // 3 K slots, 4 value slots, a dump row, level-2 sums
-    using MF = GsvMfmaA<T>;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -522,7 +467,7 @@ __global__ __launch_bounds__(256, 1) void gsv4_kernel(GsvArgs a) {
         koff[j] = (unsigned)(row * 256 + (((lane & 15) ^ (row & 15)) << 4));
     }
     const long kplane_bytes = a.k_plane_stride * 2;
-    const unsigned lds0 = gsv4_lds_addr(lds);
+    const unsigned lds0 = um_lds_addr(lds);
     const unsigned wrow = lds0 + 16 * wave * 256;                       // this wave's rows of K slot 0
     int kaddr;
     {
@@ -608,8 +553,8 @@ __global__ __launch_bounds__(256, 1) void gsv4_kernel(GsvArgs a) {
         constexpr int bq = (NS == 2) ? 0 : (ks & 1);
         constexpr int kpl = (NS == 2 && prod == 0) ? 1 : 0;      // lo_k * hi_q, hi_k * lo_q, hi_k * hi_q
         constexpr int qpl = (NS == 2 && prod == 1) ? 1 : 0;
-        if constexpr (ks == 0 && prod == 0) MF::init(x.a[sub][qb], fr[bq][sub * NS + kpl], qf[qb][qpl][ks], cinit[qb]);
-        else MF::acc(x.a[sub][qb], fr[bq][sub * NS + kpl], qf[qb][qpl][ks]);
+        f32x16& d = x.a[sub][qb];               // the first MFMA of a tile starts from cinit (srcC), the others accumulate
+        d = T::mfma(fr[bq][sub * NS + kpl], qf[qb][qpl][ks], (ks == 0 && prod == 0) ? cinit[qb] : d);
     };
     // K fragments of the next k-step -- after the last k-step: the FIRST k-step of the next tile (slot base kb_next), so
     // that a block starts with its operands in registers.  Exact mode: ONE buffer, every fragment re-read in place right

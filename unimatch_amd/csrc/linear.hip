@@ -47,16 +47,6 @@ struct LinArgs {
     unsigned* range_flag;         // um_range_flags: sticky operand-range word (device address; nullptr: none)
 };
 
-__device__ __forceinline__ void lin_dma16(const void* base, unsigned byte_off, const unsigned char* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane(
-        (unsigned)(unsigned long)(const __attribute__((address_space(3))) unsigned char*)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(byte_off), "s"(base), "s"(dst)
-                 : "memory");
-}
-
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 
 template <class T, int NS, int ASRC, int EPI>
@@ -93,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void linear_kernel(LinArgs a) {
             const int sc = dcp ^ ((r >> 2) & 3);
             const unsigned off = (unsigned)(((long)grow * ld + k0 + 8 * sc) * 2);
 #pragma unroll
-            for (int pl = 0; pl < NS; ++pl) lin_dma16(base + pl * plane_stride, off, dst + pl * TILE + (32 * wave + 16 * i) * 64);
+            for (int pl = 0; pl < NS; ++pl) um_lds_dma16(base + pl * plane_stride, off, dst + pl * TILE + (32 * wave + 16 * i) * 64);
         }
     };
     // fp32 activations: 8 consecutive lanes read one row's 128 contiguous bytes (32 floats); 4 passes of 32 rows

@@ -46,10 +46,7 @@ extern void um_set_error(const char* fmt, ...);
 #define K4M_TW 8
 #define K4M_TH 4
 #define K4M_MAXROWS 24
-#ifndef K4S_CW
-#define K4S_CW 16                // target cell: 16 x 8 positions of f1  ->  window (16 + 10) x (8 + 10) <= 32 x 24
-#define K4S_CH 8
-#endif
+constexpr int K4S_CW = 16, K4S_CH = 8;       // target cell: 16 x 8 positions of f1  ->  window (16 + 10) x (8 + 10) <= 32 x 24
 
 struct K4mArgs {
     const float* f0;             // [B][L][128] fp32 tokens (VALU path)
@@ -284,18 +281,6 @@ __global__ __launch_bounds__(K4S_WG) void k4s_scatter_kernel(const unsigned* ctl
     }
 }
 
-
-__device__ __forceinline__ int k4m_wave_min(int v) {
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) v = min(v, __shfl_xor(v, s));
-    return v;
-}
-__device__ __forceinline__ int k4m_wave_max(int v) {
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) v = max(v, __shfl_xor(v, s));
-    return v;
-}
-
 __global__ __launch_bounds__(128) void k4m_kernel(K4mArgs a) {
     // per wave: the [slot][pixel] dot tables (one spare slot: the blend reads one past a row); the [tap][pixel] output tile
     // takes the same storage once the tables are consumed (the blends are held in registers across a wave barrier).
@@ -343,8 +328,8 @@ __global__ __launch_bounds__(128) void k4m_kernel(K4mArgs a) {
         // clamp far-away bases so the int conversion is defined; such samples are all-zero anyway
         const int bx = (int)fminf(fmaxf(fbx, -32768.f), 32768.f);
         const int by = (int)fminf(fmaxf(fby, -32768.f), 32768.f);
-        const int ux0 = k4m_wave_min(bx) - K4M_RADIUS, ux1 = k4m_wave_max(bx) - K4M_RADIUS + n1 - 1;
-        const int uy0 = k4m_wave_min(by) - K4M_RADIUS, uy1 = k4m_wave_max(by) - K4M_RADIUS + n1 - 1;
+        const int ux0 = wave_min_i(bx) - K4M_RADIUS, ux1 = wave_max_i(bx) - K4M_RADIUS + n1 - 1;
+        const int uy0 = wave_min_i(by) - K4M_RADIUS, uy1 = wave_max_i(by) - K4M_RADIUS + n1 - 1;
         const int bw = ux1 - ux0 + 1, bh = uy1 - uy0 + 1;
         const bool coherent = softmax_mode || (!a.force_valu && bw <= 32 && bh <= K4M_MAXROWS);     // wave uniform
 

@@ -505,27 +505,6 @@ __global__ __launch_bounds__(256) void depth_corr_softmax_kernel(const float* __
 // the dots is the dot with the blended row; summation order differs from the gather form by fp32 rounding only).  A box of more
 // than DEPTH_BOX rows (a camera move with a long diagonal epipolar segment) takes the gather path for that pixel.
 #define DEPTH_BOX 160
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = min(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = max(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void depth_corr_softmax_box_kernel(const float* __restrict__ f0,
                                                                      const float* __restrict__ f1,
                                                                      const float* __restrict__ cam,

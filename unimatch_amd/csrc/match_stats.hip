@@ -67,17 +67,6 @@ __device__ __forceinline__ MsState ms_merge(const MsState& a, const MsState& b) 
     return r;
 }
 
-// 16 bytes per lane, global -> LDS without passing through VGPRs (as gsv_dma16 of global_match.hip)
-__device__ __forceinline__ void ms_dma16(const void* base, unsigned byte_off, const unsigned char* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane(
-        (unsigned)(unsigned long)(const __attribute__((address_space(3))) unsigned char*)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(byte_off), "s"(base), "s"(dst)
-                 : "memory");
-}
-
 // workgroup = 4 waves = 128 queries, wave = 32 queries, key tiles of 64; 2 K slots (tile t+1 lands while tile t is consumed) and
 // 2 slots of key coordinates; one workgroup barrier per tile.  Two workgroups per CU (64 KB of LDS each in exact mode).
 template <class T, int NS, bool CAUSAL>
@@ -123,7 +112,7 @@ __global__ __launch_bounds__(256, 2) void match_stats_kernel(MsArgs a) {
                 const int row = srow + 4 * j;
                 const int key = min(t * TK + row, a.Lk - 1);
                 const unsigned off = kbase_bytes + (unsigned)key * (UM_CHANNELS * 2) + ((scp ^ (row & 15)) << 4);
-                ms_dma16(a.kp + pl * a.k_plane_stride, off, lds + slot * KSLOT + pl * PLANE + (16 * wave + 4 * j) * 256);
+                um_lds_dma16(a.kp + pl * a.k_plane_stride, off, lds + slot * KSLOT + pl * PLANE + (16 * wave + 4 * j) * 256);
             }
         if (wave == 0) {                          // pixel coordinates of the tile's keys
             float* c = reinterpret_cast<float*>(lds + CBASE + slot * CSLOT);

@@ -37,25 +37,6 @@ __device__ unsigned long long* g_um_trace = nullptr;
 #define UM_STAMP(slot) do { } while (0)
 #endif
 
-// -DUM_WATTN_P1=1 (diagnostic builds: profiles/r03_precision_budget.txt): the PV product with P in ONE fp16 plane -- 2 MFMA
-// products (V_lo.P + V_hi.P) instead of 3, no lo split of P -- and the softmax denominator summed over the SAME rounded
-// probabilities (v_dot2c_f32_f16), so that the result is an exact weighted mean with weights perturbed by <= 2^-11 relative.
-#ifndef UM_WATTN_P1
-#define UM_WATTN_P1 0
-#endif
-// Round-4 experiments on the tile loop (diagnostic builds, profiles/r04_attention_experiments.txt):
-//   UM_WATTN_DMA_POS  0: the tile's four LDS-DMA statements ride on QK^T k-steps 0, 2, 4, 6 (rounds 1-3)
-//                     1: they are issued in the softmax phase (VALU only) instead of inside an MFMA phase
-//                     2: on QK^T k-steps 1, 3, 5, 7 (the address preparation no longer stands in front of the first MFMA)
-//   UM_WATTN_OFF32    1: staging sources as 32-bit byte offsets from a scalar base (global_load_lds ... v, s[base]) instead of
-//                        64-bit per-lane pointers: half the address registers, no 64-bit arithmetic per tile
-#ifndef UM_WATTN_DMA_POS
-#define UM_WATTN_DMA_POS 0
-#endif
-#ifndef UM_WATTN_OFF32
-#define UM_WATTN_OFF32 1      // round 4: -2.7 % per launch in the model, +0.9 % end to end (profiles/r04_attention_experiments.txt)
-#endif
-
 struct WattnArgs {
     const unsigned short* qp;    // planes [NS][S][L][128]
     const unsigned short* kp;
@@ -148,20 +129,6 @@ __device__ __forceinline__ int cm_token(const WattnArgs& a, const WinClasses& k,
     return oy * a.w + ox;
 }
 
-// 16 bytes per lane, global -> LDS without passing through VGPRs: LDS address = wave-uniform dst + 16 * lane.
-// Issued through inline asm on purpose: hipcc cannot prove that the ring slot being filled and the slot being
-// read do not alias and would drain the DMA (s_waitcnt vmcnt(0)) in front of the first LDS read; hidden from its
-// scoreboard, the transfer stays in flight for the whole tile and is waited for explicitly before the barrier.
-__device__ __forceinline__ void lds_dma16(const void* gsrc, const unsigned char* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane(
-        (unsigned)(unsigned long)(const __attribute__((address_space(3))) unsigned char*)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(dst)
-                 : "memory");
-}
-
 template <class T, int NS, bool MERGE, bool QPROJ = false, bool KSPLIT = false>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void window_attn_kernel(WattnArgs a) {
     // One LDS buffer = one tile of TK window tokens: K planes, V planes (linear 256-byte rows, 16-byte chunks
@@ -249,7 +216,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             const int cw = pc ^ (row & 15);
 #pragma unroll
             for (int pl = 0; pl < NS; ++pl)
-                lds_dma16(a.wq + pl * a.wm_plane_stride + row * UM_CHANNELS + 8 * cw, lds + pl * 32768 + (4 * (8 * wave + i)) * 256);
+                um_lds_dma16_ptr(a.wq + pl * a.wm_plane_stride + row * UM_CHANNELS + 8 * cw, lds + pl * 32768 + (4 * (8 * wave + i)) * 256);
         }
     }
     const int ntiles = (a.n + TK - 1) / TK;
@@ -279,11 +246,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     //   per-lane bias table as before.
     // All wave-uniform (ballots); tile index = bit index, at most 64 tiles because the token table holds 2048 tokens.
     unsigned long long own_pure = 0, probe = 0;
-#ifdef UM_WATTN_KSPLIT_NOSKIP          // diagnostic builds: key-split launches walk every tile (the same-box A/B of profiles/r06_ksplit_skip.txt)
-    if (has_mask && use_tab && !KSPLIT) {
-#else
     if (has_mask && use_tab) {
-#endif
         const int q0 = qt * 128, q1 = min(q0 + 127, a.n - 1);
         const int cq = cm_class(wc, q0);
         if (cq == cm_class(wc, q1)) {
@@ -484,9 +447,9 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     // instructions per wave queues up in the CU's single address unit (measured: ~1100 of ~5400 cycles per
     // tile); issued one per k-step of the QK^T loop instead, each piece hides under three MFMAs.
     constexpr int NPIECE = 4 * NS;
-    const unsigned short* spk[2];
-    const unsigned short* spv[2];
-    unsigned sok[2], sov[2];                                             // UM_WATTN_OFF32: byte offsets from a.kp / a.vp
+    // staging sources: 32-bit byte offsets from the scalar bases a.kp / a.vp (global_load_lds ... v, s[base]) -- half the address
+    // registers of per-lane 64-bit pointers, no 64-bit arithmetic per tile; the launcher keeps one plane below 4 GiB
+    unsigned sok[2], sov[2];
     auto stage_prepare = [&](int t, unsigned char* base) {
         // bias[class][key]: 0, the -100 mask (raw units), or "no such key"; only tiles that need it read it
         const bool need = need_bias(t);
@@ -494,15 +457,9 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             const unsigned* tp = tab + t * TK + 8 * wave + ((lane >> 4) & 3);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                if (UM_WATTN_OFF32) {
-                    const unsigned goff = ((unsigned)kvbase + (tp[4 * j] >> 2)) * (unsigned)a.ldkv;
-                    sok[j] = 2u * (goff + (unsigned)ssrc_k[j]);
-                    sov[j] = 2u * (goff + (unsigned)ssrc_v[j]);
-                } else {
-                    const long goff = (kvbase + (long)(tp[4 * j] >> 2)) * a.ldkv;
-                    spk[j] = a.kp + goff + ssrc_k[j];
-                    spv[j] = a.vp + goff + ssrc_v[j];
-                }
+                const unsigned goff = ((unsigned)kvbase + (tp[4 * j] >> 2)) * (unsigned)a.ldkv;
+                sok[j] = 2u * (goff + (unsigned)ssrc_k[j]);
+                sov[j] = 2u * (goff + (unsigned)ssrc_v[j]);
             }
             if (need && tid < 4 * TK) {
                 const int cq = tid >> 5, key = tid & (TK - 1);
@@ -517,15 +474,9 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             int cls;
             const int tok = token_at(sly[j], slx[j], cls);
             advance(sly[j], slx[j]);
-            if (UM_WATTN_OFF32) {
-                const unsigned goff = ((unsigned)kvbase + (unsigned)tok) * (unsigned)a.ldkv;
-                sok[j] = 2u * (goff + (unsigned)ssrc_k[j]);
-                sov[j] = 2u * (goff + (unsigned)ssrc_v[j]);
-            } else {
-                const long goff = (kvbase + tok) * a.ldkv;
-                spk[j] = a.kp + goff + ssrc_k[j];
-                spv[j] = a.vp + goff + ssrc_v[j];
-            }
+            const unsigned goff = ((unsigned)kvbase + (unsigned)tok) * (unsigned)a.ldkv;
+            sok[j] = 2u * (goff + (unsigned)ssrc_k[j]);
+            sov[j] = 2u * (goff + (unsigned)ssrc_v[j]);
         }
         if (need && tid < 4 * TK) {
             const int cq = tid >> 5, key = tid & (TK - 1);
@@ -538,32 +489,22 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     };
     // one statement = the wave's two 4-row groups of one plane of K (or V): ONE M0 write, the second request carries the LDS
     // (and global) displacement of 1024 bytes in its instruction offset, so its source comes in 1024 bytes low.  M0 is saved and
-    // restored inside the statement (hipcc manages M0 itself for the prologue's / epilogue's lds_dma16 and does not honour an
-    // "m0" clobber): 6 instructions per pair instead of 10.
+    // restored inside the statement (as in um_lds_dma16, common.h): 6 instructions per pair instead of 10.
     constexpr int NPAIR = 2 * NS;
     auto stage_pair = [&](int ip, unsigned char* base) {        // ip = 0 .. NPAIR-1, compile-time after unrolling
         const int pl = ip >> 1, isv = ip & 1;
-        const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(const __attribute__((address_space(3))) unsigned char*)(
-            base + (8 * wave) * 256 + (isv * NS + pl) * PLANE));
+        const unsigned dst = um_lds_addr(base + (8 * wave) * 256 + (isv * NS + pl) * PLANE);
         unsigned keep;
-        if (UM_WATTN_OFF32) {
-            // the second request's instruction offset (1024: its LDS displacement) also moves its SOURCE: compensated in the SCALAR
-            // base, not in the offset register -- that one is zero-extended, so "offset - 1024" of a row in the first kilobyte of
-            // the plane would address 4 GiB further on
-            const unsigned short* base = (isv ? a.vp : a.kp) + pl * a.kv_plane_stride;       // wave-uniform: SGPR pair
-            const unsigned short* base1 = base - 512;
-            const unsigned o0 = isv ? sov[0] : sok[0];
-            const unsigned o1 = isv ? sov[1] : sok[1];
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-                         "global_load_lds_dwordx4 %2, %4 offset:1024\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(o0), "v"(o1), "s"(base), "s"(base1), "s"(dst) : "memory");
-            return;
-        }
-        const unsigned short* s0 = (isv ? spv[0] : spk[0]) + pl * a.kv_plane_stride;
-        const unsigned short* s1 = (isv ? spv[1] : spk[1]) + pl * a.kv_plane_stride - 512;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-                     "global_load_lds_dwordx4 %2, off offset:1024\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(s0), "v"(s1), "s"(dst) : "memory");
+        // the second request's instruction offset (1024: its LDS displacement) also moves its SOURCE: compensated in the SCALAR
+        // base, not in the offset register -- that one is zero-extended, so "offset - 1024" of a row in the first kilobyte of
+        // the plane would address 4 GiB further on
+        const unsigned short* src = (isv ? a.vp : a.kp) + pl * a.kv_plane_stride;       // wave-uniform: SGPR pair
+        const unsigned short* src1 = src - 512;
+        const unsigned o0 = isv ? sov[0] : sok[0];
+        const unsigned o1 = isv ? sov[1] : sok[1];
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
+                     "global_load_lds_dwordx4 %2, %4 offset:1024\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(o0), "v"(o1), "s"(src), "s"(src1), "s"(dst) : "memory");
     };
 
     const int li = lane & 15, lg = (lane >> 4) & 1;
@@ -606,9 +547,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                     fh[(ks + 2) % 3] = *reinterpret_cast<const i16x8*>(kb + koff[ks + 2]);
                     if (NS == 2) fl[(ks + 2) % 3] = *reinterpret_cast<const i16x8*>(kb + PLANE + koff[ks + 2]);
                 }
-                if (UM_WATTN_DMA_POS == 0 && staging && (ks * NPAIR) % 8 == 0) stage_pair(ks * NPAIR / 8, nxt);
-                if (UM_WATTN_DMA_POS == 2 && staging && NPAIR == 4 && (ks & 1)) stage_pair(ks >> 1, nxt);   // k-steps 1, 3, 5, 7
-                if (UM_WATTN_DMA_POS == 2 && staging && NPAIR == 2 && (ks == 3 || ks == 7)) stage_pair(ks >> 2, nxt);
+                if (staging && (ks * NPAIR) % 8 == 0) stage_pair(ks * NPAIR / 8, nxt);       // k-steps 0, 2, 4, 6 (one plane: 0, 4)
                 if (NS == 2) {
                     sc = T::mfma(fl[ks % 3], qf[0][ks], sc);
                     sc = T::mfma(fh[ks % 3], qf[NS - 1][ks], sc);
@@ -641,7 +580,6 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         }
 
         // ---- online softmax (row max shared by the lane pair l, l^32) ------------------------------------
-        if (UM_WATTN_DMA_POS == 1 && staging) stage_pair(0, nxt);
         float mx = sc[0];
 #pragma unroll
         for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sc[r]);
@@ -651,7 +589,6 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             mx = fmaxf(u, v2);
         }
         m = fmaxf(m, mx);
-        if (UM_WATTN_DMA_POS == 1 && staging && NPAIR > 1) stage_pair(1, nxt);
         // Lazy, exact rescale.  The exponent offset M is an integer (every rescale factor is a power of two) and
         // is allowed to lag the true running max by up to LAG: then p <= 2^(LAG + PSHIFT) = 2^15 still fits fp16,
         // and the 64-accumulator rescale -- which otherwise fires on almost every tile because SOME of the wave's
@@ -674,18 +611,14 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
                 for (int r = 0; r < 16; ++r) o[dt][r] *= resc;
         }
-        if (UM_WATTN_DMA_POS == 1 && staging && NPAIR > 2) stage_pair(2, nxt);
-        constexpr bool P1 = (NS == 2) && UM_WATTN_P1;           // one P plane (see UM_WATTN_P1)
-        constexpr int NSP = P1 ? 1 : NS;
         const float mc = M + (float)PSHIFT;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float p = fast_exp2(__builtin_fmaf(sc[r], c, mc));
             sc[r] = p;
-            if (!P1) l += p;
+            l += p;
         }
 
-        if (UM_WATTN_DMA_POS == 1 && staging && NPAIR > 3) stage_pair(3, nxt);
         // ---- P^T operand fragments: cvt + v_permlane32_swap, no LDS ---------------------------------------
         // k-step ks (16 keys) uses regs 8*ks..8*ks+7; after the swaps a lane holds keys 8*half .. 8*half+7 of
         // the step for its own query (B operand layout).
@@ -698,11 +631,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             for (int j = 0; j < 4; ++j) {
                 const float p0 = sc[r0 + 2 * j], p1 = sc[r0 + 2 * j + 1];
                 wh[j] = T::pack2(p0, p1);
-                if (NSP == 2) wl[j] = T::lo2(p0, p1, wh[j], neg1);
-                if constexpr (P1) {
-                    const f16x2 one = {(_Float16)1.0f, (_Float16)1.0f};
-                    l = __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, wh[j]), one, l, false);
-                }
+                if (NS == 2) wl[j] = T::lo2(p0, p1, wh[j], neg1);
             }
             {
                 const auto x = __builtin_amdgcn_permlane32_swap(wh[0], wh[2], false, false);
@@ -710,7 +639,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 const u32x4 f = {x[0], y[0], x[1], y[1]};
                 pf[0][ks] = __builtin_bit_cast(i16x8, f);
             }
-            if (NSP == 2) {
+            if (NS == 2) {
                 const auto x = __builtin_amdgcn_permlane32_swap(wl[0], wl[2], false, false);
                 const auto y = __builtin_amdgcn_permlane32_swap(wl[1], wl[3], false, false);
                 const u32x4 f = {x[0], y[0], x[1], y[1]};
@@ -742,13 +671,13 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                         (__attribute__((address_space(3))) i16x4*)(va + PLANE + 4 * 256));
                     vl = __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7);
                     o[dt] = T::mfma(vl, pf[0][ks], o[dt]);
-                    if (NSP == 2) o[dt] = T::mfma(vh, pf[NS - 1][ks], o[dt]);
+                    o[dt] = T::mfma(vh, pf[NS - 1][ks], o[dt]);
                 }
                 o[dt] = T::mfma(vh, pf[0][ks], o[dt]);
             }
         }
         {   // transpose reads two (k-step, d-tile) groups ahead of the MFMAs
-            constexpr int RD = 2 * NS, MF = NS + NSP - 1;
+            constexpr int RD = 2 * NS, MF = 2 * NS - 1;
             __builtin_amdgcn_sched_group_barrier(0x100, 2 * RD, 1);
 #pragma unroll
             for (int g = 0; g < 6; ++g) {
@@ -796,9 +725,6 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             }
         }
         if (pass == 1 || probe == 0) break;
-#ifdef UM_WATTN_ASSUME_PASS          // diagnostic builds ONLY (wrong results for adversarial inputs): what the probe phase costs
-        break;                       // (profiles/r06_probe_cost.txt)
-#endif
 
         // ---- probe phase.  Every key of a `probe` tile is of another class than all 128 queries of the workgroup: its logit is
         // q.k / sqrt(C) - 100.  The own-class tiles are done, so m (the running row maximum, raw units) is a lower bound of the
@@ -830,8 +756,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                     const unsigned* tp = tab + last_tile * TK + 8 * wave + ((lane >> 4) & 3);
                     const unsigned o0 = 2u * (((unsigned)kvbase + (tp[0] >> 2)) * (unsigned)a.ldkv + (unsigned)ssrc_k[0]);
                     const unsigned o1 = 2u * (((unsigned)kvbase + (tp[4] >> 2)) * (unsigned)a.ldkv + (unsigned)ssrc_k[1]);
-                    const unsigned dst = __builtin_amdgcn_readfirstlane(
-                        (unsigned)(unsigned long)(const __attribute__((address_space(3))) unsigned char*)(base + i * PLANE + (8 * wave) * 256));
+                    const unsigned dst = um_lds_addr(base + i * PLANE + (8 * wave) * 256);
                     const unsigned short* b0 = a.kp;
                     const unsigned short* b1 = a.kp - 512;
                     unsigned keep;
@@ -995,7 +920,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             const int c = pc ^ (row & 15);
 #pragma unroll
             for (int pl = 0; pl < NS; ++pl)
-                lds_dma16(a.wm + pl * a.wm_plane_stride + row * UM_CHANNELS + 8 * c, lds + pl * 32768 + (4 * (8 * wave + i)) * 256);
+                um_lds_dma16_ptr(a.wm + pl * a.wm_plane_stride + row * UM_CHANNELS + 8 * c, lds + pl * 32768 + (4 * (8 * wave + i)) * 256);
         }
     }
     i16x8 of[NS][8];
@@ -1350,8 +1275,8 @@ static int launch_window_attn(const unsigned short* pq, const unsigned short* pk
                               int win_h, int win_w, int shift_h, int shift_w, int kv_rotate, int mode, hipStream_t stream,
                               const unsigned short* wm, const float* gamma, const float* beta, const float* residual,
                               float eps, int wshift, const float* x, const unsigned short* wq, void* ks_ws, size_t ks_ws_bytes) {
-    // the staging sources are 32-bit byte offsets from the k / v plane bases (UM_WATTN_OFF32): one plane must stay below 4 GiB
-    if (UM_WATTN_OFF32 && (long)streams * h * w * ldkv * 2 >= (1L << 32)) {
+    // the staging sources are 32-bit byte offsets from the k / v plane bases: one plane must stay below 4 GiB
+    if ((long)streams * h * w * ldkv * 2 >= (1L << 32)) {
         um_set_error("window attention: a k / v operand plane of %ld bytes is beyond the 4 GiB this kernel addresses",
                      (long)streams * h * w * ldkv * 2);
         return UM_ERR_UNSUPPORTED;
