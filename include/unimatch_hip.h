@@ -782,6 +782,63 @@ int um_points_pack(const float* depth, const float* cam_world, const float* keep
                    unsigned char* rgb, int* count, int batch, int h, int w, int stride, float min_depth, float max_depth, void* workspace,
                    size_t ws_bytes, void* stream);
 
+/* Frame synthesis from flow (csrc/interp.hip): apply a flow to the frames it was computed from.  A classical synthesis with no learned
+ * part.  Memory-bound, one thread per pixel; every entry point enqueues on `stream` and never synchronises; nothing is kept between
+ * calls.  fp32 arithmetic with every product, sum and quotient rounded on its own, float64 and int64 where stated; each entry point
+ * is bitwise equal to its host restatement (unimatch_amd/interp.py).  Images are UM_IMG_F32_NCHW [B,C,H,W] fp32 or UM_IMG_U8_NHWC
+ * [B,H,W,3] uint8; flows [B,2,H,W] fp32 (x, y); h, w >= 2; batch <= 65535.  A null pointer (where not stated as optional), a bad size
+ * or a workspace that is too small returns UM_ERR_BAD_ARG and names the entry point in um_last_error_string.  NaN, infinite or huge
+ * flows never cause an out-of-bounds access: taps are taken from clamped addresses and discarded.
+ *   um_image_warp        out(p) = bilinear(image, p + flow(p)), the reference's flow_warp (unimatch/geometry.py:41-72) on an image:
+ *                        out has the layout and type of image (uint8: rint of the fp32 sum, clamped to 0..255; channels == 3 there).
+ *                        The position goes through the reference's normalise / un-normalise round trip (g = 2 p / (n - 1) - 1,
+ *                        i = ((g + 1) / 2) (n - 1)), as in um_fwd_bwd_occlusion.  border == 0: taps outside the frame add nothing
+ *                        (grid_sample's zeros padding); border != 0: the position is clamped into [0, w - 1] x [0, h - 1] first (a
+ *                        NaN goes to 0).  mask (optional, [B,H,W] bytes in {0, 1}): the reference's return_mask, -1 <= g <= 1 in x
+ *                        and y (before the clamp).  h * w <= 2^30.
+ *   um_flow_splat        forward splatting of one or two flow fields (flow_bwd, weight_fwd, weight_bwd optional) to k <=
+ *                        UM_INTERP_MAX_TIMES times each.  times: a HOST array [dirs][k] (dirs = 2 with flow_bwd, else 1), every
+ *                        value strictly between 0 and 1; it is read before the call returns.  Source pixel p = (x, y) with flow
+ *                        (u, v) lands at X = (float)x + t u, Y = (float)y + t v; ax = X - floor(X), ay likewise; its four taps
+ *                        (1 - ax)(1 - ay), ax (1 - ay), (1 - ax) ay, ax ay are multiplied by weight[b, y, x] ([B,H,W] fp32, clamped
+ *                        to <= 1; a weight that is NaN, infinite or <= 0 contributes nothing) and every in-frame tap adds, with
+ *                        wq = (int64) rint(wt 65536), uq = (int64) rint(256 u), vq likewise:  S_w += wq, S_u += wq uq, S_v += wq vq.
+ *                        A pixel whose flow is not finite or exceeds 32768 px in either component contributes nothing.  The sums are
+ *                        64-bit INTEGER atomic adds: they commute, so the accumulators are bitwise reproducible from run to run
+ *                        (float atomic sums depend on arrival order).  workspace (8-byte aligned) receives them as int64
+ *                        [dirs][B][k][3][H][W] (planes S_w, S_u, S_v) and must hold um_flow_splat_workspace_bytes(batch, dirs, k,
+ *                        h, w) bytes (0 for bad sizes).  The entry point clears the workspace itself on `stream` before the launch:
+ *                        safe under graph capture, and no launch reads what an earlier call left behind.  |S| <= H W 2^39, so
+ *                        H * W IS CAPPED AT 2^21 here (2^30 elsewhere would let the sums pass 2^63); batch * dirs * k <= 65535.
+ *                        Optional outputs (a second launch when either is given): avg_out [dirs][B][k][2][H][W] fp32 =
+ *                        (float)((double)S_u / (double)S_w / 256.0) (v likewise), and hole_out [dirs][B][k][H][W] bytes in {0, 1} =
+ *                        S_w < max(1, rint(min_weight 65536)) (the product in fp32; 0 <= min_weight <= 1); avg_out is 0 in a hole.
+ *   um_frame_synthesize  k in-between frames of every pair: out [B][k][H][W][3] uint8 and, optionally, holes [B][k][H][W] bytes.
+ *                        img0, img1 in either layout (C = 3, values 0..255); accum: the accumulators of um_flow_splat for dirs = 2
+ *                        with times = [t_0 .. t_k-1 | 1 - t_0 .. 1 - t_k-1] (the same HOST array is passed here); occ_fwd, occ_bwd
+ *                        optional [B,H,W] fp32, 1 = occluded (um_fwd_bwd_occlusion).  Per output pixel q and time t, with
+ *                        t' = times[1][.]:
+ *                          1. A = the forward flow splatted to t, B = the backward flow splatted to t', each valid where its S_w
+ *                             reaches the hole threshold; m = 0.5 (A + (-B)) when both are valid, A or -B when one is, else 0 and
+ *                             q is a hole;
+ *                          2. c0 = bilinear(img0, q - t m), c1 = bilinear(img1, q + t' m), positions clamped into the frame;
+ *                             v0, v1 = the unclamped position lies in [0, w - 1] x [0, h - 1];
+ *                          3. o0 = occ_fwd at q - t m, o1 = occ_bwd at q + t' m (bilinear, zeros outside; 0 without masks);
+ *                          4. w0 = v0 ? t' (1 - o1) : 0, w1 = v1 ? t (1 - o0) : 0; if !(w0 + w1 >= 1e-6): w0 = t', w1 = t;
+ *                          5. out = rint((w0 c0 + w1 c1) / (w0 + w1)) clamped to 0..255.
+ *                        Bilinear taps NW, NE, SW, SE with the weights (x1 - x)(y1 - y) ... of um_fwd_bwd_occlusion, summed in
+ *                        that order.  Same limits as um_flow_splat; accum_bytes >= um_flow_splat_workspace_bytes(batch, 2, k, h, w). */
+#define UM_INTERP_MAX_TIMES 16
+int um_image_warp(const void* image, int layout, const float* flow, void* out, unsigned char* mask, int batch, int channels, int h,
+                  int w, int border, void* stream);
+size_t um_flow_splat_workspace_bytes(int batch, int dirs, int k, int h, int w);
+int um_flow_splat(const float* flow_fwd, const float* flow_bwd, const float* weight_fwd, const float* weight_bwd, const float* times,
+                  int batch, int k, int h, int w, float min_weight, float* avg_out, unsigned char* hole_out, void* workspace,
+                  size_t ws_bytes, void* stream);
+int um_frame_synthesize(const void* img0, const void* img1, int layout, const float* occ_fwd, const float* occ_bwd, const float* times,
+                        const void* accum, size_t accum_bytes, unsigned char* out, unsigned char* holes, int batch, int k, int h, int w,
+                        float min_weight, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Encoder helper (outside the hot path of SURVEY.md section 8; added because the element-wise tail of the CNN encoder
  * had become the largest non-convolution cost):  fused InstanceNorm2d(affine=False) + ReLU (+ shortcut + ReLU),

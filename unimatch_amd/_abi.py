@@ -82,6 +82,12 @@ SIGNATURES = {
     'um_flow_to_rgb_workspace_bytes': (_c_size_t, [_c_int] * 3),
     'um_flow_to_rgb': (_c_int, [_c_void_p] * 2 + [_c_int] * 3 + [_c_void_p, _c_size_t, _c_void_p]),
     'um_flow_chain': (_c_int, [_c_void_p] * 6 + [_c_int] * 5 + [_c_void_p]),
+    'um_image_warp': (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p] + [_c_int] * 5 + [_c_void_p]),
+    'um_flow_splat_workspace_bytes': (_c_size_t, [_c_int] * 5),
+    'um_flow_splat': (_c_int, [_c_void_p] * 4 + [ctypes.POINTER(ctypes.c_float)] + [_c_int] * 4 + [ctypes.c_float, _c_void_p, _c_void_p,
+                                _c_void_p, _c_size_t, _c_void_p]),
+    'um_frame_synthesize': (_c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, ctypes.POINTER(ctypes.c_float), _c_void_p,
+                                      _c_size_t, _c_void_p, _c_void_p] + [_c_int] * 4 + [ctypes.c_float, _c_void_p]),
     'um_flow_metrics_workspace_bytes': (_c_size_t, [_c_int] * 3),
     'um_flow_metrics': (_c_int, [_c_void_p] * 5 + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p]),
     'um_disp_metrics_workspace_bytes': (_c_size_t, [_c_int] * 3),

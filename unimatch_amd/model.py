@@ -651,7 +651,7 @@ class UniMatch(nn.Module):
                          num_reg_refine=1, pred_bidir_flow=False, consistency_check=False, colorize=False, pairs_per_launch=8,
                          carry=None, task='flow', intrinsics=None, poses=None, min_depth=1. / 0.5, max_depth=1. / 10,
                          num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, track_points=None,
-                         return_confidence=False):
+                         return_confidence=False, interpolate=0):
         """Optical flow of every pair (t, t+1) of a frame sequence ``frames [T, 3, H, W]`` (raw 0..255), each frame encoded ONCE.
 
         The reference's ``inference_flow`` (evaluate_flow.py:640-831) runs the model on each pair, so every interior frame goes through
@@ -678,6 +678,12 @@ class UniMatch(nn.Module):
         in the same forward at the chunk's global matching step: ``max_prob``, ``entropy``, ``variance``, ``best`` ``[P, h, w]`` of
         the forward direction, ``scale`` and, with ``pred_bidir_flow``, ``mutual`` ``[P, h, w]``.  A chunk then runs as one part.
 
+        ``interpolate`` K >= 1 (flow only, needs ``pred_bidir_flow``): the result gains ``'frames_between'`` ``[P, K, H, W, 3]`` uint8,
+        the K frames at the times ``k / (K + 1)`` between the two frames of every pair (:func:`interp.interpolate_frames`: a classical
+        synthesis by flow splatting, backward warps and an occlusion-aware blend, with no learned part).  It is computed per chunk
+        right after the chunk's flows (two launches), from the chunk's own frames and its occlusion masks (those of
+        ``consistency_check`` / tracking, computed once).  0: nothing is launched and every other output is unchanged.
+
         ``task='depth'``: the depth of every frame t of a posed video from the pair (t, t + 1) -- the one other task whose consecutive
         pairs share a frame (a stereo pair shares nothing with the next one: ``task='stereo'`` raises).  ``frames`` are what
         :meth:`forward` takes for depth (normalised already), ``poses [T, 4, 4]`` the frames' absolute camera-to-world matrices and
@@ -700,6 +706,12 @@ class UniMatch(nn.Module):
             raise ValueError("track_points follows points through optical flow: it needs task='flow'")
         if task == 'depth' and return_confidence:
             raise NotImplementedError("return_confidence: task='depth' matches by a plane sweep, which has its own distribution")
+        if isinstance(interpolate, bool) or not isinstance(interpolate, int) or not 0 <= interpolate <= 16:
+            raise ValueError(f'interpolate: expected an int in 0 .. 16 (in-between frames per pair), got {interpolate!r}')
+        if interpolate and task == 'depth':
+            raise ValueError("interpolate synthesises frames from optical flow: it needs task='flow'")
+        if interpolate and not pred_bidir_flow:
+            raise ValueError('interpolate needs pred_bidir_flow=True (the flows of both directions)')
         if return_confidence and -1 not in (corr_radius_list or ()):
             raise ValueError('return_confidence needs a global matching step (a corr_radius of -1 in corr_radius_list)')
         if task == 'depth':
@@ -729,6 +741,8 @@ class UniMatch(nn.Module):
         assert len(attn_splits_list) == len(corr_radius_list) == len(prop_radius_list) == self.num_scales
         import contextlib
         from . import video
+        if interpolate:
+            from . import interp
         dev = frames.device
         ops = self.ops
         if self.check_weights:
@@ -738,13 +752,16 @@ class UniMatch(nn.Module):
             _abi.check_operand_range('an earlier forward of this process: ')
         guard = torch.cuda.device(dev) if frames.is_cuda else contextlib.nullcontext()
         step = int(pairs_per_launch)
-        out = {k: [] for k in ('flow', 'flow_bwd', 'occ_fwd', 'occ_bwd', 'flow_rgb', 'flow_bwd_rgb', 'tracks', 'tracks_visible')}
+        out = {k: [] for k in ('flow', 'flow_bwd', 'occ_fwd', 'occ_bwd', 'flow_rgb', 'flow_bwd_rgb', 'tracks', 'tracks_visible',
+                               'frames_between')}
         confs = []                                        # per chunk: the matching step's confidence dict
         with guard, torch.no_grad():
             prev = None                                   # per-scale features [1, C, h, w] of the frame before frames[i]
+            before = None                                 # that frame itself: the first image of the next chunk's first pair
             if carry is not None:
                 if self._carry_valid(carry, frames):
                     prev = carry['features']
+                    before = carry['frame'].to(dev)
                 else:                                     # stale: the stored frame is encoded with the first chunk
                     frames = torch.cat([carry['frame'].to(dev), frames], 0)
             i = 0                                         # first frame of the next chunk's new frames
@@ -766,7 +783,7 @@ class UniMatch(nn.Module):
                 if pred_bidir_flow:
                     bwd = pred[nb:]
                     out['flow_bwd'].append(bwd)
-                    if consistency_check or track is not None:
+                    if consistency_check or track is not None or interpolate:
                         occ_f, occ_b = video.forward_backward_consistency_check(fwd, bwd)
                     if consistency_check:
                         out['occ_fwd'].append(occ_f)
@@ -776,6 +793,12 @@ class UniMatch(nn.Module):
                     out['tracks'].append(trk)
                     out['tracks_visible'].append(vis)
                     track = (trk[-1], vis[-1], 1)
+                if interpolate:
+                    seen = new if before is None else torch.cat([before, new], 0)      # the chunk's nb + 1 frames
+                    out['frames_between'].append(interp.interpolate_frames(
+                        seen[:-1].float().contiguous(), seen[1:].float().contiguous(), fwd, bwd, interp.between_times(interpolate),
+                        occ_fwd=occ_f, occ_bwd=occ_b))
+                before = new[new.shape[0] - 1:]
                 if colorize:
                     out['flow_rgb'].append(video.flow_to_image(fwd))
                     if pred_bidir_flow:

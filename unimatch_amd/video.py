@@ -11,7 +11,9 @@ the normalisation on, as NumPy 2 promotes); the CPU tests pin it against fixture
 ``python -m unimatch_amd.video --frames DIR --out DIR [...]`` runs :meth:`UniMatch.forward_sequence` over the ``*.png`` / ``*.jpg``
 frames of a directory (sorted) and writes the reference's file set: ``%04d_flow.png``, ``%04d_flow_bwd.png``, ``%04d_occ_fwd.png`` /
 ``%04d_occ_bwd.png`` and ``%04d_pred.flo`` (``%04d_pred_bwd.flo``); ``--track-grid S`` adds ``tracks.npz``, the tracks of every S-th
-pixel of the first frame through the whole directory.  Reading frames needs PIL; video containers are not supported.
+pixel of the first frame through the whole directory; ``--interpolate K`` adds ``%04d_tNNN.png``, K in-between frames of every pair
+(:func:`interp.interpolate_frames`: a classical, unlearned synthesis), and ``--save-warped`` ``%04d_warped.png``, the pair's second
+frame warped back onto the first by the forward flow.  Reading frames needs PIL; video containers are not supported.
 """
 import argparse
 import glob
@@ -250,18 +252,28 @@ def read_frame_u8(path):
 
 
 def run_directory(model, paths, out_dir, fwd_kw, padding_factor=8, inference_size=None, pred_bidir_flow=False, fwd_bwd_check=False,
-                  save_flo=False, pairs_per_launch=8, device='cuda', device_resize=False, track_grid=0, save_confidence=False):
+                  save_flo=False, pairs_per_launch=8, device='cuda', device_resize=False, track_grid=0, save_confidence=False,
+                  interpolate=0, save_warped=False):
     """``inference_flow`` over the frames ``paths`` with the sequence mode: returns the number of pairs written.  ``device_resize``:
     upload the frames as uint8 and transpose / resize / resize back through :class:`unimatch_amd.prepost.InferenceGeometry` (one
     launch per step) instead of an fp32 upload and torch ops; the files written have the same names and the same format.
     ``track_grid`` S > 0: follow every S-th pixel of the first frame through the restored flows (:func:`chain_flows`, with the forward
     occlusion mask when ``pred_bidir_flow``) and write ``tracks.npz``: ``tracks [T-1, N, 2]``, ``visible [T-1, N]``, ``start [N, 2]``.
     ``save_confidence``: also write ``<stem>_conf.png``, the peak matching probability of every feature pixel
-    (``forward_sequence(return_confidence=True)``: taken in the same forward) nearest-upsampled to the frame and coloured."""
+    (``forward_sequence(return_confidence=True)``: taken in the same forward) nearest-upsampled to the frame and coloured.
+    ``interpolate`` K > 0 (needs ``pred_bidir_flow``): also write ``<stem>_tNNN.png``, the K frames at the times ``t = k / (K + 1)``
+    between the pair's two frames, ``NNN = round(1000 t)`` (:func:`interp.interpolate_frames` on the restored, frame-size flows and
+    their occlusion masks).  ``save_warped``: also write ``<stem>_warped.png``, the pair's second frame warped back by the forward
+    flow with zeros padding (:func:`interp.backward_warp`): where the flow is right it looks like the first frame."""
     from .io import write_flo, write_png8
     from .prepost import InferenceGeometry
     if fwd_bwd_check and not pred_bidir_flow:
         raise ValueError('--fwd-bwd-check needs --pred-bidir-flow (as the reference asserts)')
+    if interpolate and not pred_bidir_flow:
+        raise ValueError('--interpolate needs --pred-bidir-flow (the flows of both directions)')
+    if interpolate or save_warped:
+        from . import interp
+    last_raw = None                                                     # the previous chunk's last frame as it was read
     os.makedirs(out_dir, exist_ok=True)
     carry, pair = None, 0
     track, tracks, visible = None, [], []                               # (positions, alive) after the last pair; per-chunk rows
@@ -272,13 +284,13 @@ def run_directory(model, paths, out_dir, fwd_kw, padding_factor=8, inference_siz
         i += len(take)
         geom = None
         if device_resize:
-            frames = torch.stack([read_frame_u8(p) for p in take], 0).to(device)
+            frames = raw = torch.stack([read_frame_u8(p) for p in take], 0).to(device)
             geom = (InferenceGeometry.resized(frames.shape[1:3], inference_size, transpose='auto') if inference_size else
                     InferenceGeometry.nearest(frames.shape[1:3], padding_factor, transpose='auto'))
             frames, = geom.prepare(frames)
             transpose, size, ori = False, None, None                    # the geometry has done, and will undo, all of it
         else:
-            frames = torch.stack([read_frame(p) for p in take], 0).to(device)
+            frames = raw = torch.stack([read_frame(p) for p in take], 0).to(device)
             transpose = frames.shape[-2] > frames.shape[-1]             # the model is trained with width > height
             if transpose:
                 frames = frames.transpose(-2, -1)
@@ -309,13 +321,34 @@ def run_directory(model, paths, out_dir, fwd_kw, padding_factor=8, inference_siz
             flows = [f.transpose(-2, -1) for f in flows]
         rgbs = [flow_to_image(f.contiguous()).cpu().numpy() for f in flows]
         occ = None
-        if fwd_bwd_check or (track_grid and pred_bidir_flow):
+        if fwd_bwd_check or ((track_grid or interpolate) and pred_bidir_flow):
             occ = forward_backward_consistency_check(flows[0].contiguous(), flows[1].contiguous())
         if track_grid:
             trk, vis = chain_flows(flows[0].contiguous(), None if occ is None else occ[0], *(track or (None, None)), stride=track_grid)
             track = (trk[-1], vis[-1])
             tracks.append(trk.cpu().numpy())
             visible.append(vis.cpu().numpy())
+        between = warped = None
+        if interpolate or save_warped:                                  # on the frames as they were read, in either upload layout
+            seen = raw if last_raw is None else torch.cat([last_raw, raw], 0)
+            last_raw = raw[raw.shape[0] - 1:]
+            tall = transpose or (geom is not None and geom.transpose)
+            u8 = seen.dtype == torch.uint8
+            use, use_occ = [f.contiguous() for f in flows], occ
+            if tall:            # the flow's channels are those of the transposed image (the restore leaves them so): work there
+                seen = seen.transpose(1, 2) if u8 else seen.transpose(-2, -1)
+                use = [f.transpose(-2, -1).contiguous() for f in flows]
+                use_occ = forward_backward_consistency_check(*use) if interpolate else None
+            first, second = seen[:-1].contiguous(), seen[1:].contiguous()
+            if interpolate:
+                times = interp.between_times(interpolate)
+                between = interp.interpolate_frames(first, second, use[0], use[1], times, occ_fwd=use_occ[0], occ_bwd=use_occ[1])
+                between = (between.transpose(2, 3) if tall else between).cpu().numpy()
+            if save_warped:
+                warped = interp.backward_warp(second, use[0])
+                if not u8:                                              # fp32 upload: [P, 3, H, W] in 0..255
+                    warped = warped.round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1)
+                warped = (warped.transpose(1, 2) if tall else warped).cpu().numpy()
         if not fwd_bwd_check:
             occ = None
         host = [f.permute(0, 2, 3, 1).cpu().numpy() for f in flows]
@@ -329,6 +362,11 @@ def run_directory(model, paths, out_dir, fwd_kw, padding_factor=8, inference_siz
                 write_png8(name + '_occ_bwd.png', (occ[1][j].cpu().numpy() * 255.).astype(np.uint8))
             if conf_rgb is not None:
                 write_png8(name + '_conf.png', conf_rgb[j])
+            if between is not None:
+                for n, t in enumerate(times):
+                    write_png8(name + '_t%03d.png' % round(1000 * t), np.ascontiguousarray(between[j, n]))
+            if warped is not None:
+                write_png8(name + '_warped.png', np.ascontiguousarray(warped[j]))
             if save_flo:
                 write_flo(name + '_pred.flo', host[0][j])
                 if pred_bidir_flow:
@@ -362,6 +400,11 @@ def main(argv=None):
                          '--pred-bidir-flow a track also ends where the forward occlusion mask covers it')
     ap.add_argument('--save-confidence', action='store_true',
                     help='write <stem>_conf.png: the peak matching probability of every feature pixel, nearest-upsampled to the frame')
+    ap.add_argument('--interpolate', type=int, default=0, metavar='K',
+                    help='write <stem>_tNNN.png: K in-between frames of every pair at the times k / (K + 1), NNN = round(1000 t); a '
+                         'classical synthesis from the two flows (no learned part), needs --pred-bidir-flow')
+    ap.add_argument('--save-warped', action='store_true',
+                    help='write <stem>_warped.png: the next frame warped back by the forward flow (zeros outside the frame)')
     ap.add_argument('--device-resize', action='store_true', help='upload uint8 frames; transpose, resize and resize back on the device')
     args = ap.parse_args(argv)
     paths = list_frames(args.frames)
@@ -381,7 +424,7 @@ def main(argv=None):
     n = run_directory(model, paths, args.out, fwd_kw, padding_factor=args.padding_factor, inference_size=args.inference_size,
                       pred_bidir_flow=args.pred_bidir_flow, fwd_bwd_check=args.fwd_bwd_check, save_flo=args.save_flo,
                       pairs_per_launch=args.pairs_per_launch, device_resize=args.device_resize, track_grid=args.track_grid,
-                      save_confidence=args.save_confidence)
+                      save_confidence=args.save_confidence, interpolate=args.interpolate, save_warped=args.save_warped)
     print(f'{n} pairs written to {args.out}')
 
 
