@@ -561,6 +561,23 @@ int um_depth_corr_softmax(const float* f0, const float* f1, const float* cam, co
                           float* out, int batch, int h, int w, int channels, int num_candidates,
                           int from_argmax, void* stream);
 
+/* um_depth_corr_softmax plus the statistics of the distribution it reduces, in the same launch.  The reference returns
+ * that distribution -- correlation_softmax_depth gives (depth, match_prob [B, D, h, w]), matching.py:227 -- and the plane
+ * sweep here never forms it.  f0 .. out and from_argmax as above (same kernels, same arithmetic for `out`).  With
+ * p_j = softmax_j(logit_j) over the D candidates c_j of a pixel:
+ *   stats [B, 4, h, w] fp32:  0 max_prob = max_j p_j | 1 entropy = -sum p ln p (nats, 0 .. ln D) |
+ *                             2 variance = sum p_j (c_j - mu)^2 about mu = sum p_j c_j (inverse depth squared) |
+ *                             3 peak_mass = sum of p_j over |j - best| <= peak_radius (radius 0: max_prob)
+ *   index [B, 2, h, w] int32: 0 best = the first j attaining the maximum logit (what from_argmax reads out) |
+ *                             1 in_view = candidates with a bilinear corner inside the image (0: every logit is exactly 0,
+ *                               the distribution is uniform)
+ * stats or index may be NULL: that output is not written.  Errors (negative, nothing launched): a null f0 / f1 / cam /
+ * candidates / out, channels != 128, num_candidates outside 1 .. 128, peak_radius < 0. */
+int um_depth_corr_softmax_stats(const float* f0, const float* f1, const float* cam, const float* candidates,
+                                float* out, float* stats, int* index,
+                                int batch, int h, int w, int channels, int num_candidates,
+                                int from_argmax, int peak_radius, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * RAFT convex upsampling (SURVEY.md 8(f) "next" row): softmax over the 9 neighbours of each of factor^2 sub-pixels,
  * weighted sum of the 3x3 (zero padded) neighbourhood of mult * flow, pixel shuffle.  Replaces

@@ -131,6 +131,7 @@ SIGNATURES = {
     'um_local_corr_with_flow_feat': (_c_int, [_c_void_p] * 6 + [_c_int, ctypes.c_long] + [_c_int] * 6 + [_c_void_p, _c_void_p]),
     'um_prop_local_attn': (_c_int, [_c_void_p] * 4 + [_c_int] * 6 + [_c_void_p]),
     'um_depth_corr_softmax': (_c_int, [_c_void_p] * 5 + [_c_int] * 6 + [_c_void_p]),
+    'um_depth_corr_softmax_stats': (_c_int, [_c_void_p] * 7 + [_c_int] * 7 + [_c_void_p]),
     'um_census_enable': (_c_int, [_c_int]),
     'um_census_count': (ctypes.c_long, [_c_int]),
     'um_window_attn_tile_census': (_c_int, [_c_int, ctypes.POINTER(ctypes.c_ulonglong)]),

@@ -39,6 +39,9 @@ EXTRA_FLAGS = {'ffn.hip': ['-fno-slp-vectorize'], 'global_match.hip': ['-fno-slp
 # build reads the compiler's resource report for these sources and fails if a named kernel spills to scratch or loses occupancy,
 # instead of shipping a silently slower kernel.  source -> {substring of the mangled kernel name: minimum waves per SIMD}
 RESOURCE_GUARDS = {'conv.hip': {'conv_entry_kernel': 2},
+                   # the plane sweep (K7), plain and with statistics: no scratch in any of the four kernels, three waves per SIMD as before the statistics
+                   'local_ops.hip': {'depth_corr_softmax_kernel': 3, 'depth_corr_softmax_box_kernel': 3, 'depth_corr_softmax_stats_kernel': 3,
+                                     'depth_corr_softmax_box_stats_kernel': 3},
                    # memory-bound per-pixel kernels: no scratch, and registers far below what would cost a wave
                    'geometry.hip': {'disp_consistency_kernel': 4, 'depth_consistency_kernel': 4, 'points_count_kernel': 4,
                                     'points_scan_kernel': 4, 'points_scatter_kernel': 4},

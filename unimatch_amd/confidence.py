@@ -17,6 +17,21 @@ the query's scanline (stereo):
 CUDA tensors run ``um_global_match_stats`` / ``um_match_mutual`` (csrc/match_stats.hip); host tensors run the ``*_host`` restatements
 below, plain torch that forms ``prob`` and follows the dtype of its inputs (the tests evaluate it in float64).  There is no silent
 fallback from one to the other.
+
+Depth has its own distribution: the plane sweep's ``match_prob [B, D, h, w]`` over the D inverse-depth candidates of a pixel
+(``correlation_softmax_depth`` gives ``(depth, match_prob)``, matching.py:203-236), which the sweep's kernels reduce to one number.
+
+  depth_match_stats(f0, f1, h, w, cam, candidates, peak_radius=)  ``DepthMatchStats`` of every pixel: ``max_prob``, ``entropy``, ``variance =
+                                                                  sum_j p_j (c_j - mu)^2`` about the soft-argmin ``mu`` (inverse depth^2),
+                                                                  ``peak_mass`` = the probability within ``peak_radius`` candidates of
+                                                                  ``best`` (the first arg-max candidate), ``in_view`` = candidates with
+                                                                  a bilinear corner inside the image (0: all logits 0, uniform)
+  depth_match_confidence(ops, ...)                                the sweep's prediction and the ``'depth_confidence'`` dict of
+                                                                  ``UniMatch.forward_with_depth_confidence``
+  confidence_to_image_size(map, scale, geom)                      a feature-resolution map at image size
+
+CUDA tensors run ``um_depth_corr_softmax_stats`` (csrc/local_ops.hip: the sweep's own launch also writes the statistics); host tensors
+run ``depth_match_prob_host`` / ``depth_stats_from_prob_host``, the reference's ``match_prob`` from the packed camera record.
 """
 from collections import namedtuple
 
@@ -150,6 +165,155 @@ def match_confidence(tok0, tok1, h, w, task, bidir, scale, precision='exact'):
         b = tok0.shape[0]
         out['mutual'] = mutual_matches(s.best[:b], s.best[b:], h, w, 0)
     return out
+
+
+# ------------------------------------------------------------------ depth: the plane sweep's distribution
+DepthMatchStats = namedtuple('DepthMatchStats', 'max_prob entropy variance peak_mass best in_view')
+DepthMatchStats.__doc__ = ('Statistics of the plane sweep\'s ``match_prob`` (unimatch/matching.py:227) over the D inverse-depth candidates of '
+                           'every pixel: ``max_prob``, ``entropy`` (nats), ``variance`` (about the soft-argmin, inverse depth squared), '
+                           '``peak_mass`` (the probability within ``peak_radius`` candidates of the best one) ``[B, h, w]`` float; ``best`` '
+                           '(first arg-max candidate) and ``in_view`` (candidates with a bilinear corner inside the image; 0: a uniform '
+                           'distribution) ``[B, h, w]`` int32.')
+
+
+def _check_depth_inputs(f0, f1, h, w, cam, candidates):
+    _check_features(f0, f1, h, w)
+    if tuple(cam.shape) != (f0.shape[0], 30) or cam.device != f0.device:
+        raise ValueError(f'cam: expected [{f0.shape[0]}, 30] = K^-1 | R | t | K on {f0.device}, got {tuple(cam.shape)} on {cam.device}')
+    if candidates.dim() != 1 or not 1 <= candidates.numel() <= 128 or candidates.device != f0.device:
+        raise ValueError(f'candidates: expected 1 .. 128 inverse depths [D] on {f0.device}, got {tuple(candidates.shape)} on {candidates.device}')
+
+
+def depth_sample_coords_host(h, w, cam, candidates):
+    """Where every candidate of every pixel lands in the second view: ``(sx, sy)`` ``[B, D, h, w]`` in feature pixels, in ``cam``'s dtype
+    and in the kernel's operation order (back-project, rotate, scale by depth, translate, project, clamp ``z >= 1e-3``)."""
+    dt, dev = cam.dtype, cam.device
+    b = cam.shape[0]
+    kinv, rot, trans, k = cam[:, 0:9].view(b, 3, 3), cam[:, 9:18].view(b, 3, 3), cam[:, 18:21], cam[:, 21:30].view(b, 3, 3)
+    gy, gx = torch.meshgrid(torch.arange(h, dtype=dt, device=dev), torch.arange(w, dtype=dt, device=dev), indexing='ij')
+
+    def mat(m, x, y, z):                                                   # rows of m [B, 3, 3] times (x, y, z), left to right
+        return [m[:, i, 0].view(b, 1, 1, 1) * x + m[:, i, 1].view(b, 1, 1, 1) * y + m[:, i, 2].view(b, 1, 1, 1) * z for i in range(3)]
+
+    r = mat(kinv, gx.view(1, 1, h, w), gy.view(1, 1, h, w), torch.ones((), dtype=dt, device=dev))
+    q = mat(rot, *r)
+    depth = (1.0 / candidates.to(dt)).view(1, -1, 1, 1)
+    x, y, z = (q[i] * depth + trans[:, i].view(b, 1, 1, 1) for i in range(3))
+    u, v, zz = mat(k, x, y, z)
+    zz = zz.clamp(min=1e-3)
+    return (u / zz).clamp(-1.0e6, 1.0e6), (v / zz).clamp(-1.0e6, 1.0e6)
+
+
+def depth_match_logits_host(f0, f1, h, w, cam, candidates):
+    """``(logits [B, D, h, w], in_view [B, h, w] int32)`` of the plane sweep: feature1 sampled bilinearly with zero padding where each
+    candidate lands, correlated with feature0, over ``sqrt(C)``.  ``in_view`` counts the candidates with a corner inside the image."""
+    _check_depth_inputs(f0, f1, h, w, cam, candidates)
+    b, l, c = f0.shape
+    dt = f0.dtype
+    sx, sy = depth_sample_coords_host(h, w, cam.to(dt), candidates)
+    fx0, fy0 = torch.floor(sx), torch.floor(sy)
+    wx, wy = sx - fx0, sy - fy0
+    x0, y0 = fx0.long(), fy0.long()
+    d = x0.shape[1]
+    a = f0.view(b, 1, l, c)
+    corr = torch.zeros((b, d, l), dtype=dt, device=f0.device)
+    batch = torch.arange(b, device=f0.device).view(b, 1, 1)
+    for cy in (0, 1):
+        for cx in (0, 1):
+            yy, xx = (y0 + cy).view(b, d, l), (x0 + cx).view(b, d, l)
+            ok = (yy >= 0) & (yy < h) & (xx >= 0) & (xx < w)
+            wt = ((wx if cx else 1 - wx) * (wy if cy else 1 - wy)).view(b, d, l)
+            rows = f1[batch, (yy.clamp(0, h - 1) * w + xx.clamp(0, w - 1))]            # [B, D, L, C]
+            corr = corr + torch.where(ok, wt * (a * rows).sum(-1), torch.zeros((), dtype=dt, device=f0.device))
+    seen = ((x0 >= -1) & (x0 < w) & (y0 >= -1) & (y0 < h)).sum(1).to(torch.int32)
+    return (corr / c ** 0.5).view(b, d, h, w), seen
+
+
+def depth_match_prob_host(f0, f1, h, w, cam, candidates):
+    """The reference's ``match_prob`` ``[B, D, h, w]`` (``correlation_softmax_depth``, unimatch/matching.py:203-236) from token-major
+    features ``[B, h*w, C]`` and the packed ``cam [B, 30]`` = K^-1 | R | t | K record, in the dtype of the features."""
+    return torch.softmax(depth_match_logits_host(f0, f1, h, w, cam, candidates)[0], 1)
+
+
+def depth_stats_from_prob_host(prob, candidates, in_view, peak_radius):
+    """``DepthMatchStats`` of a given ``prob [B, D, h, w]``, in its dtype (``in_view`` is passed through)."""
+    if int(peak_radius) < 0:
+        raise ValueError(f'peak_radius must be >= 0, got {peak_radius}')
+    dt, dev = prob.dtype, prob.device
+    d = prob.shape[1]
+    max_prob, best = prob.max(1)                                           # the first maximal index, as the kernel
+    plogp = torch.where(prob > 0, prob * torch.log(prob.clamp(min=torch.finfo(dt).tiny)), torch.zeros_like(prob))
+    entropy = (-plogp.sum(1)).clamp(min=0)
+    cand = candidates.to(dt).view(1, d, 1, 1)
+    mu = (prob * cand).sum(1, keepdim=True)
+    variance = (prob * (cand - mu) ** 2).sum(1)
+    j = torch.arange(d, device=dev).view(1, d, 1, 1)
+    window = (j - best[:, None]).abs() <= int(peak_radius)
+    peak_mass = torch.where(window, prob, torch.zeros_like(prob)).sum(1)   # radius 0: one term and zeros, max_prob exactly
+    return DepthMatchStats(max_prob, entropy, variance, peak_mass, best.to(torch.int32), in_view)
+
+
+def depth_match_stats_host(f0, f1, h, w, cam, candidates, peak_radius=1):
+    """:func:`depth_match_stats` as a plain torch composition that forms ``match_prob``, in the dtype and on the device of the inputs."""
+    logits, seen = depth_match_logits_host(f0, f1, h, w, cam, candidates)
+    return depth_stats_from_prob_host(torch.softmax(logits, 1), candidates, seen, peak_radius)
+
+
+def depth_match_stats(f0, f1, h, w, cam, candidates, *, peak_radius=1):
+    """``DepthMatchStats`` of the plane sweep of the token-major features ``f0``, ``f1`` ``[B, h*w, 128]`` under ``cam [B, 30]`` over the
+    inverse-depth ``candidates [D]``.  CUDA tensors run ``um_depth_corr_softmax_stats`` (the sweep's own launch, its prediction
+    discarded); host tensors run the restatement above.  There is no fallback from one to the other."""
+    _check_depth_inputs(f0, f1, h, w, cam, candidates)
+    if int(peak_radius) < 0:
+        raise ValueError(f'peak_radius must be >= 0, got {peak_radius}')
+    if not f0.is_cuda:
+        return depth_match_stats_host(f0, f1, h, w, cam, candidates, int(peak_radius))
+    return _depth_sweep_device(f0, f1, h, w, cam, candidates, False, int(peak_radius))[1]
+
+
+def _depth_sweep_device(f0, f1, h, w, cam, candidates, from_argmax, peak_radius, ops=None):
+    """``(out [B, 1, h, w], DepthMatchStats)`` of one ``um_depth_corr_softmax_stats`` launch; through ``ops`` (a ``HipOps``: its launch
+    record sees the call) when given."""
+    if ops is not None:
+        out, stats, index = ops.depth_corr_softmax(f0, f1, h, w, cam, candidates, from_argmax, stats=True, peak_radius=peak_radius)
+    else:
+        lib = _abi.load()                    # raises when the HIP extension is missing: there is no silent fallback
+        tensors = (f0, f1, cam, candidates)
+        if not all(t.dtype == torch.float32 and t.is_contiguous() for t in tensors):
+            raise ValueError('expected contiguous CUDA float32 features, cam and candidates')
+        b, l, c = f0.shape
+        with torch.cuda.device(f0.device):
+            out = torch.empty((b, 1, h, w), dtype=torch.float32, device=f0.device)
+            stats = torch.empty((b, 4, h, w), dtype=torch.float32, device=f0.device)
+            index = torch.empty((b, 2, h, w), dtype=torch.int32, device=f0.device)
+            _abi.check(lib.um_depth_corr_softmax_stats(f0.data_ptr(), f1.data_ptr(), cam.data_ptr(), candidates.data_ptr(), out.data_ptr(),
+                                                       stats.data_ptr(), index.data_ptr(), b, h, w, c, candidates.numel(),
+                                                       int(bool(from_argmax)), int(peak_radius), torch.cuda.current_stream().cuda_stream),
+                       'um_depth_corr_softmax_stats')
+    return out, DepthMatchStats(stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3], index[:, 0], index[:, 1])
+
+
+def depth_match_confidence(ops, f0, f1, h, w, cam, candidates, from_argmax, scale, peak_radius=1):
+    """The plane sweep's prediction and the ``'depth_confidence'`` dict of ``UniMatch.forward_with_depth_confidence``:
+    ``(out [B, 1, h, w], dict)``.  On the GPU both come from the one fused launch of ``ops``; on host tensors the prediction comes from
+    the backend ``ops`` as in :meth:`forward` and the statistics from the host restatement."""
+    if int(peak_radius) < 0:
+        raise ValueError(f'peak_radius must be >= 0, got {peak_radius}')
+    if f0.is_cuda:
+        out, s = _depth_sweep_device(f0.contiguous(), f1.contiguous(), h, w, cam, candidates, from_argmax, int(peak_radius), ops)
+    else:
+        out = ops.depth_corr_softmax(f0, f1, h, w, cam, candidates, from_argmax)
+        s = depth_match_stats_host(f0, f1, h, w, cam, candidates, int(peak_radius))
+    conf = dict(s._asdict(), scale=int(scale), num_candidates=int(candidates.numel()))
+    return out, conf
+
+
+def confidence_to_image_size(conf_map, scale, geom=None):
+    """A feature-resolution map ``[B, h, w]`` at image size: nearest upsampling by ``scale`` (the dict's stride), then -- with ``geom``,
+    the ``prepost.InferenceGeometry`` the images were prepared with -- ``geom.restore(., 'depth')``, which crops or resizes without
+    rescaling values.  ``[B, H, W]`` float32."""
+    up = torch.nn.functional.interpolate(conf_map[:, None].float(), scale_factor=int(scale), mode='nearest')[:, 0].contiguous()
+    return up if geom is None else geom.restore(up, 'depth')
 
 
 def confidence_to_image(max_prob, size):

@@ -4,6 +4,7 @@
 //   um_local_corr_with_flow   unimatch/matching.py:86-123           (2r+1)^2 bilinear taps at p + d + flow(p)
 //   um_prop_local_attn        unimatch/attention.py:217-253         (2r+1)^2 zero-padded self-attention taps
 //   um_depth_corr_softmax     unimatch/matching.py:203-282          D plane-sweep candidates, soft-argmin
+//   um_depth_corr_softmax_stats  the same launch + statistics of match_prob (matching.py:227), which is never formed
 //
 // These are gather + short-reduction kernels (arithmetic intensity of a few flop/byte): they are bounded by
 // L2/HBM bandwidth and VALU issue, not by the matrix cores, so they are NOT reshaped into GEMMs.  The
@@ -392,9 +393,50 @@ __global__ __launch_bounds__(256) void prop_local_attn_kernel(const float* __res
 // One pixel by plain gathers (the wave's lanes = 16 candidate slots x 4 channel quarters, four bilinear corners of every candidate
 // fetched from f1: 4 x 512 B per candidate).  Serves launches with more than 64 candidates and the pixels whose candidates' corner
 // set does not fit the box table of depth_corr_softmax_box_kernel.  Returns the pixel's result on every lane.
+//
+// STATS (um_depth_corr_softmax_stats): the same pixel also yields the statistics of its distribution p_j = e_j / sum e, from the
+// logits still in registers (DepthPixelStats, on every lane).  With e_j = exp(logit_j - max) the maximum's e is exactly 1, so
+// max_prob = 1 / sum e, entropy = ln(sum e) - sum e_j (logit_j - max) / sum e, and variance and peak_mass are second per-slot
+// accumulations (about the mean; over the window around the first arg-max) reduced over the slots like sum e.  peak_mass sums the
+// same e in the same order as sum e: radius 0 gives max_prob and a radius >= D gives 1, bit for bit.  The plain instantiation
+// (STATS = false) is the kernel as it was: same arithmetic, same order, same register count.
+struct DepthPixelStats {
+    float max_prob, entropy, variance, peak_mass;
+    int best, in_view;
+};
+
+// ln of the softmax denominator (1 <= v <= 128), once per pixel.  v = m 2^k with m in [0.75, 1.5): k ln 2 carries the size and is
+// formed in two pieces (k * hi is exact: hi has 16 significant bits), logf(m) is small, so its error is a fraction of an ulp of the
+// result.  A uniform distribution (sum e = D exactly, every other term of the entropy 0) then gives ln D to within one ulp; logf(v)
+// alone is 1.06 ulp off at D = 17, and a log through fp64 costs the box kernel a wave of occupancy (173 VGPRs).
+__device__ __forceinline__ float depth_ln(float v) {
+    int k;
+    float m = frexpf(v, &k);                                   // m in [0.5, 1)
+    if (m < 0.75f) { m *= 2.f; k -= 1; }
+    const float kf = (float)k;
+    return __builtin_fmaf(kf, 0.693145751953125f, __builtin_fmaf(kf, 1.428606765330187e-06f, logf(m)));
+}
+
+__device__ __forceinline__ int slot_sum_i(int v) {
+    v += __shfl_xor(v, 4);
+    v += __shfl_xor(v, 8);
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    return v;
+}
+__device__ __forceinline__ int slot_min_i(int v) {
+    v = min(v, __shfl_xor(v, 4));
+    v = min(v, __shfl_xor(v, 8));
+    v = min(v, __shfl_xor(v, 16));
+    v = min(v, __shfl_xor(v, 32));
+    return v;
+}
+
+template <bool STATS>
 __device__ __forceinline__ float depth_pixel_gather(const float* __restrict__ f0, const float* __restrict__ f1, const float* cm,
                                                     const float* __restrict__ cand, long pid, int b, int h, int w, int nd,
-                                                    int from_argmax, float q0, float q1, float q2, int lane) {
+                                                    int from_argmax, float q0, float q1, float q2, int lane,
+                                                    int peak_radius, DepthPixelStats& st) {
     const int slot = lane >> 2, quarter = lane & 3;
     const int L = h * w;
     const int rounds = (nd + 15) >> 4;
@@ -403,6 +445,7 @@ __device__ __forceinline__ float depth_pixel_gather(const float* __restrict__ f0
     load32(a, f0 + pid * UM_CHANNELS + 4 * quarter);
     float logit[LOCAL_MAX_ROUNDS], cv[LOCAL_MAX_ROUNDS];
     float mx = -3.0e38f;
+    int seen = 0;                                      // STATS: this slot's candidates with a bilinear corner inside the image
 #pragma unroll
     for (int r = 0; r < LOCAL_MAX_ROUNDS; ++r) {
         logit[r] = -3.0e38f;
@@ -422,6 +465,7 @@ __device__ __forceinline__ float depth_pixel_gather(const float* __restrict__ f0
             const float fx0 = floorf(sx), fy0 = floorf(sy);
             const float wx = sx - fx0, wy = sy - fy0;
             const int x0 = (int)fx0, y0 = (int)fy0;
+            if constexpr (STATS) seen += (tap && x0 >= -1 && x0 < w && y0 >= -1 && y0 < h) ? 1 : 0;
             float d = 0.f;
             if (tap) {
 #pragma unroll
@@ -442,6 +486,7 @@ __device__ __forceinline__ float depth_pixel_gather(const float* __restrict__ f0
     }
     mx = slot_max(mx);
     float sp = 0.f, sc = 0.f;
+    float sl = 0.f;                                    // STATS: sum e (logit - max)
     float best = -3.0e38f;
     int besti = 0x7fffffff;
 #pragma unroll
@@ -452,12 +497,39 @@ __device__ __forceinline__ float depth_pixel_gather(const float* __restrict__ f0
             sp += e;
             sc += e * cv[r];
             if (t < nd && logit[r] > best) { best = logit[r]; besti = t; }
+            if constexpr (STATS) {
+                sl += t < nd ? e * (logit[r] - mx) : 0.f;
+                logit[r] = e;                          // the second pass below needs e, not the logit
+            }
         }
     }
     sp = slot_sum(sp);
     sc = slot_sum(sc);
     float res = sc / sp;
-    if (from_argmax) {   // first index attaining the maximum
+    if constexpr (STATS) {
+        const int mi = slot_min_i((best == mx) ? besti : 0x7fffffff);     // first index attaining the maximum
+        const float mu = res;
+        float sv = 0.f, sm = 0.f;
+#pragma unroll
+        for (int r = 0; r < LOCAL_MAX_ROUNDS; ++r) {
+            if (r < rounds) {
+                const int t = r * 16 + slot;
+                const float dc = cv[r] - mu;
+                sv += logit[r] * (dc * dc);
+                sm += abs(t - mi) <= peak_radius ? logit[r] : 0.f;
+            }
+        }
+        sl = slot_sum(sl);
+        sv = slot_sum(sv);
+        sm = slot_sum(sm);
+        st.max_prob = 1.0f / sp;
+        st.entropy = fmaxf(depth_ln(sp) - sl / sp, 0.f);
+        st.variance = sv / sp;
+        st.peak_mass = sm / sp;
+        st.best = mi;
+        st.in_view = slot_sum_i(seen);
+        if (from_argmax) res = cand[mi];
+    } else if (from_argmax) {   // first index attaining the maximum
         const int cand_i = (best == mx) ? besti : 0x7fffffff;
         int mi = cand_i;
         mi = min(mi, __shfl_xor(mi, 4));
@@ -469,12 +541,28 @@ __device__ __forceinline__ float depth_pixel_gather(const float* __restrict__ f0
     return res;
 }
 
-__global__ __launch_bounds__(256) void depth_corr_softmax_kernel(const float* __restrict__ f0,
-                                                                 const float* __restrict__ f1,
-                                                                 const float* __restrict__ cam,
-                                                                 const float* __restrict__ cand,
-                                                                 float* __restrict__ out, int batch, int h, int w,
-                                                                 int nd, int from_argmax) {
+// lane 0 of the pixel's wave writes the statistics planes (stats [B, 4, h, w], index [B, 2, h, w]; either may be null)
+__device__ __forceinline__ void depth_stats_store(float* __restrict__ stats, int* __restrict__ index, int b, int p, int L,
+                                                  const DepthPixelStats& st) {
+    if (stats) {
+        float* sp = stats + (long)b * 4 * L + p;
+        sp[0] = st.max_prob;
+        sp[L] = st.entropy;
+        sp[2 * (long)L] = st.variance;
+        sp[3 * (long)L] = st.peak_mass;
+    }
+    if (index) {
+        int* ip = index + (long)b * 2 * L + p;
+        ip[0] = st.best;
+        ip[L] = st.in_view;
+    }
+}
+
+template <bool STATS>
+__device__ __forceinline__ void depth_corr_softmax_body(const float* __restrict__ f0, const float* __restrict__ f1,
+                                                        const float* __restrict__ cam, const float* __restrict__ cand,
+                                                        float* __restrict__ out, int batch, int h, int w, int nd, int from_argmax,
+                                                        float* __restrict__ stats, int* __restrict__ index, int peak_radius) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int L = h * w;
     const long total = (long)batch * L;
@@ -490,9 +578,32 @@ __global__ __launch_bounds__(256) void depth_corr_softmax_kernel(const float* __
         const float q0 = cm[9] * r0 + cm[10] * r1 + cm[11] * r2;
         const float q1 = cm[12] * r0 + cm[13] * r1 + cm[14] * r2;
         const float q2 = cm[15] * r0 + cm[16] * r1 + cm[17] * r2;
-        const float res = depth_pixel_gather(f0, f1, cm, cand, pid, b, h, w, nd, from_argmax, q0, q1, q2, lane);
-        if (lane == 0) out[pid] = res;
+        DepthPixelStats st;
+        const float res = depth_pixel_gather<STATS>(f0, f1, cm, cand, pid, b, h, w, nd, from_argmax, q0, q1, q2, lane, peak_radius, st);
+        if (lane == 0) {
+            out[pid] = res;
+            if constexpr (STATS) depth_stats_store(stats, index, b, p, L, st);
+        }
     }
+}
+
+// The plain kernel keeps its name, its arguments, its arithmetic and its register count; the statistics are a sibling kernel.
+__global__ __launch_bounds__(256) void depth_corr_softmax_kernel(const float* __restrict__ f0,
+                                                                 const float* __restrict__ f1,
+                                                                 const float* __restrict__ cam,
+                                                                 const float* __restrict__ cand,
+                                                                 float* __restrict__ out, int batch, int h, int w,
+                                                                 int nd, int from_argmax) {
+    depth_corr_softmax_body<false>(f0, f1, cam, cand, out, batch, h, w, nd, from_argmax, nullptr, nullptr, 0);
+}
+__global__ __launch_bounds__(256) void depth_corr_softmax_stats_kernel(const float* __restrict__ f0,
+                                                                       const float* __restrict__ f1,
+                                                                       const float* __restrict__ cam,
+                                                                       const float* __restrict__ cand,
+                                                                       float* __restrict__ out, int batch, int h, int w,
+                                                                       int nd, int from_argmax, float* __restrict__ stats,
+                                                                       int* __restrict__ index, int peak_radius) {
+    depth_corr_softmax_body<true>(f0, f1, cam, cand, out, batch, h, w, nd, from_argmax, stats, index, peak_radius);
 }
 
 // Round 4: the plane sweep by its integer neighbourhood (as the cost volume, matching.py:86-123, has been since round 1).  The
@@ -504,13 +615,13 @@ __global__ __launch_bounds__(256) void depth_corr_softmax_kernel(const float* __
 // wave-private LDS table, and every candidate blends its four corners from the table (a dot product is linear in f1, so the blend of
 // the dots is the dot with the blended row; summation order differs from the gather form by fp32 rounding only).  A box of more
 // than DEPTH_BOX rows (a camera move with a long diagonal epipolar segment) takes the gather path for that pixel.
+// STATS: lane = candidate, so the statistics (see depth_pixel_gather) are wave reductions of per-lane values.
 #define DEPTH_BOX 160
-__global__ __launch_bounds__(256) void depth_corr_softmax_box_kernel(const float* __restrict__ f0,
-                                                                     const float* __restrict__ f1,
-                                                                     const float* __restrict__ cam,
-                                                                     const float* __restrict__ cand,
-                                                                     float* __restrict__ out, int batch, int h, int w,
-                                                                     int nd, int from_argmax) {
+template <bool STATS>
+__device__ __forceinline__ void depth_corr_softmax_box_body(const float* __restrict__ f0, const float* __restrict__ f1,
+                                                            const float* __restrict__ cam, const float* __restrict__ cand,
+                                                            float* __restrict__ out, int batch, int h, int w, int nd, int from_argmax,
+                                                            float* __restrict__ stats, int* __restrict__ index, int peak_radius) {
     __shared__ float tab_all[4][DEPTH_BOX];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int slot = lane >> 2, quarter = lane & 3;
@@ -549,8 +660,9 @@ __global__ __launch_bounds__(256) void depth_corr_softmax_box_kernel(const float
         const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
         const int npos = bw * bh;
         float res;
+        DepthPixelStats st;
         if (npos > DEPTH_BOX) {                              // wave-uniform
-            res = depth_pixel_gather(f0, f1, cm, cand, pid, b, h, w, nd, from_argmax, q0, q1, q2, lane);
+            res = depth_pixel_gather<STATS>(f0, f1, cm, cand, pid, b, h, w, nd, from_argmax, q0, q1, q2, lane, peak_radius, st);
         } else {
             f32x4 a[8];
             load32(a, f0 + pid * UM_CHANNELS + 4 * quarter);
@@ -589,13 +701,47 @@ __global__ __launch_bounds__(256) void depth_corr_softmax_box_kernel(const float
             const float e = tap ? __expf(logit - mx) : 0.f;
             const float sp = wave_sum_f(e), sc = wave_sum_f(e * ci);
             res = sc / sp;
-            if (from_argmax) {                                   // first index attaining the maximum
+            if constexpr (STATS) {
+                const int mi = wave_min_i((tap && logit == mx) ? lane : 0x7fffffff);     // first index attaining the maximum
+                const float dc = ci - res;
+                const float sl = wave_sum_f(tap ? e * (logit - mx) : 0.f);
+                const float sv = wave_sum_f(e * (dc * dc));
+                const float sm = wave_sum_f(abs(lane - mi) <= peak_radius ? e : 0.f);
+                st.max_prob = 1.0f / sp;
+                st.entropy = fmaxf(depth_ln(sp) - sl / sp, 0.f);
+                st.variance = sv / sp;
+                st.peak_mass = sm / sp;
+                st.best = mi;
+                st.in_view = __popcll(__ballot(tap && x0 >= -1 && x0 < w && y0 >= -1 && y0 < h));
+                if (from_argmax) res = cand[mi];
+            } else if (from_argmax) {                            // first index attaining the maximum
                 const int mi = wave_min_i((tap && logit == mx) ? lane : 0x7fffffff);
                 res = cand[mi];
             }
         }
-        if (lane == 0) out[pid] = res;
+        if (lane == 0) {
+            out[pid] = res;
+            if constexpr (STATS) depth_stats_store(stats, index, b, p, L, st);
+        }
     }
+}
+
+__global__ __launch_bounds__(256) void depth_corr_softmax_box_kernel(const float* __restrict__ f0,
+                                                                     const float* __restrict__ f1,
+                                                                     const float* __restrict__ cam,
+                                                                     const float* __restrict__ cand,
+                                                                     float* __restrict__ out, int batch, int h, int w,
+                                                                     int nd, int from_argmax) {
+    depth_corr_softmax_box_body<false>(f0, f1, cam, cand, out, batch, h, w, nd, from_argmax, nullptr, nullptr, 0);
+}
+__global__ __launch_bounds__(256) void depth_corr_softmax_box_stats_kernel(const float* __restrict__ f0,
+                                                                           const float* __restrict__ f1,
+                                                                           const float* __restrict__ cam,
+                                                                           const float* __restrict__ cand,
+                                                                           float* __restrict__ out, int batch, int h, int w,
+                                                                           int nd, int from_argmax, float* __restrict__ stats,
+                                                                           int* __restrict__ index, int peak_radius) {
+    depth_corr_softmax_box_body<true>(f0, f1, cam, cand, out, batch, h, w, nd, from_argmax, stats, index, peak_radius);
 }
 
 // ------------------------------------------------------------------------------------ host side
@@ -769,5 +915,36 @@ extern "C" int um_depth_corr_softmax(const float* f0, const float* f1, const flo
     else
         hipLaunchKernelGGL(depth_corr_softmax_kernel, dim3(pixel_grid_blocks((long)batch * h * w)), dim3(256), 0,
                            (hipStream_t)stream, f0, f1, cam, candidates, out, batch, h, w, num_candidates, from_argmax);
+    return (int)hipGetLastError();
+}
+
+// The plane sweep and the statistics of its distribution in ONE launch (the sibling kernels: the same bodies with STATS): `out` as
+// um_depth_corr_softmax, stats [B, 4, h, w] = max_prob | entropy | variance | peak_mass, index [B, 2, h, w] = best | in_view.
+extern "C" int um_depth_corr_softmax_stats(const float* f0, const float* f1, const float* cam, const float* candidates,
+                                           float* out, float* stats, int* index, int batch, int h, int w, int channels,
+                                           int num_candidates, int from_argmax, int peak_radius, void* stream) {
+    if (int e = local_check(f0, f1, out, batch, h, w, channels)) return e;
+    if (!cam || !candidates) {
+        um_set_error("um_depth_corr_softmax_stats: null pointer (cam=%p candidates=%p)", (const void*)cam, (const void*)candidates);
+        return -1;
+    }
+    if (num_candidates < 1 || num_candidates > 16 * LOCAL_MAX_ROUNDS) {
+        um_set_error("num_candidates=%d unsupported (1..%d)", num_candidates, 16 * LOCAL_MAX_ROUNDS);
+        return -4;
+    }
+    if (peak_radius < 0) {
+        um_set_error("peak_radius=%d: the window around the best candidate needs a radius >= 0", peak_radius);
+        return -4;
+    }
+    ScopedKernelTimer timer(UM_K_DEPTH_CORR, (hipStream_t)stream);
+    static const bool no_box = um_debug_env("UM_DEPTH_NO_BOX") != nullptr;     // A/B switch (diagnostic builds)
+    if (num_candidates <= 64 && !no_box)
+        hipLaunchKernelGGL(depth_corr_softmax_box_stats_kernel, dim3(pixel_grid_blocks((long)batch * h * w)), dim3(256), 0,
+                           (hipStream_t)stream, f0, f1, cam, candidates, out, batch, h, w, num_candidates, from_argmax,
+                           stats, index, peak_radius);
+    else
+        hipLaunchKernelGGL(depth_corr_softmax_stats_kernel, dim3(pixel_grid_blocks((long)batch * h * w)), dim3(256), 0,
+                           (hipStream_t)stream, f0, f1, cam, candidates, out, batch, h, w, num_candidates, from_argmax,
+                           stats, index, peak_radius);
     return (int)hipGetLastError();
 }

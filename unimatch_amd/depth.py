@@ -22,6 +22,13 @@ Values and geometry (both modes write the same files):
                             frame) agree with its depth to ``--px-thr`` pixels and ``--rel-thr`` relative depth, 0 where the pixel is kept
   ``--save-ply FILE``       the fused, consistency-filtered, coloured world point cloud of the whole scene (binary PLY), every
                             ``--ply-stride``-th pixel of every row and column (:func:`unimatch_amd.geometry.fuse_depth_sequence`)
+  ``--save-confidence``     ``<stem>_conf.png``: the plane sweep's ``max_prob`` (``UniMatch.forward_with_depth_confidence``, statistics
+                            of the distribution over the depth candidates, window ``--peak-radius``), coloured per frame
+  ``--min-confidence P``    with ``--save-ply``: a pixel also needs ``peak_mass >= P`` (the probability within ``--peak-radius``
+                            candidates of the best one) -- a filter that needs no neighbouring frame.  With
+                            ``--pred-bidir-depth`` the last frame's depth is the last pair's backward prediction: the pairwise mode
+                            filters it on that prediction's own ``peak_mass``, ``--pairs-per-launch`` keeps the forward maps only
+                            and leaves that one frame to the consistency check alone, so the two modes' clouds can differ in it
 
 Frame i has a depth map through the pair (i, i + 1); the last frame has one only with ``--pred-bidir-depth``, through the last pair's
 backward prediction, and gets its ``_depth.png`` / ``_occ.png`` then.  The geometry always uses the depth restored to the frames' own
@@ -64,7 +71,9 @@ class _SceneCollector:
     """What ``--save-depth``, ``--consistency-check`` and ``--save-ply`` need of a scene: writes each restored depth map as it
     arrives and, for the latter two, keeps it and its uint8 frame on the device until :meth:`finish` fuses the scene."""
 
-    def __init__(self, out_dir, imgs, poses, k, save_depth, consistency_check, save_ply, ply_stride, min_views, px_thr, rel_thr):
+    def __init__(self, out_dir, imgs, poses, k, save_depth, consistency_check, save_ply, ply_stride, min_views, px_thr, rel_thr,
+                 min_confidence=None):
+        self.min_confidence, self.conf = min_confidence, []
         self.out_dir, self.imgs, self.poses, self.k = out_dir, imgs, poses, k
         self.save_depth, self.consistency_check, self.save_ply = save_depth, consistency_check, save_ply
         self.ply_stride, self.min_views, self.px_thr, self.rel_thr = ply_stride, min_views, px_thr, rel_thr
@@ -74,8 +83,9 @@ class _SceneCollector:
     def stem(self, i):
         return os.path.join(self.out_dir, os.path.splitext(os.path.basename(self.imgs[i]))[0])
 
-    def add(self, i, depth, frame_u8):
-        """Frame ``i`` (they arrive in order): its restored depth ``[H, W]`` fp32 and its frame ``[H, W, 3]`` uint8, on one device."""
+    def add(self, i, depth, frame_u8, peak_mass=None):
+        """Frame ``i`` (they arrive in order): its restored depth ``[H, W]`` fp32 and its frame ``[H, W, 3]`` uint8, on one device;
+        ``peak_mass [H, W]`` at the frame's size when the cloud is filtered on it."""
         from .io import write_png16
         if self.save_depth:
             mm = torch.nan_to_num(depth * 1000., nan=0., posinf=0., neginf=0.).round().clamp(0., 65535.)
@@ -87,6 +97,8 @@ class _SceneCollector:
                                  '--consistency-check / --save-ply need frames of one size')
             self.depths.append(depth)
             self.frames.append(frame_u8)
+            if self.min_confidence is not None:
+                self.conf.append(peak_mass)
 
     def finish(self):
         from .geometry import fuse_depth_sequence
@@ -99,7 +111,9 @@ class _SceneCollector:
         depths, colors = torch.stack(self.depths, 0), torch.stack(self.frames, 0)
         dev = depths.device
         out = fuse_depth_sequence(depths, torch.from_numpy(self.k)[None].to(dev), torch.from_numpy(self.poses[:n]).to(dev), colors,
-                                  px_thr=self.px_thr, rel_thr=self.rel_thr, min_views=self.min_views, stride=self.ply_stride)
+                                  px_thr=self.px_thr, rel_thr=self.rel_thr, min_views=self.min_views, stride=self.ply_stride,
+                                  **({} if self.min_confidence is None else
+                                     {'confidence': torch.stack(self.conf, 0), 'min_confidence': self.min_confidence}))
         if self.consistency_check:
             occ = ((1. - out['keep']) * 255.).to(torch.uint8).cpu().numpy()
             for i in range(n):
@@ -111,25 +125,31 @@ class _SceneCollector:
 def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_size=None, min_depth=0.5, max_depth=10.,
               num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, scale_intrinsics=False, device='cuda',
               pairs_per_launch=None, save_depth=False, consistency_check=False, save_ply=None, ply_stride=1, min_views=1, px_thr=1.0,
-              rel_thr=0.01):
+              rel_thr=0.01, save_confidence=False, min_confidence=None, peak_radius=1):
     """``inference_depth`` over the scene: returns the number of frames written (one less than the scene has).
     ``pairs_per_launch=N``: sequence mode (the module docstring), in pieces of N pairs; ``None``: one ``predict`` per pair.
-    ``save_depth``, ``consistency_check``, ``save_ply`` (a file name): the value and geometry outputs of the module docstring."""
+    ``save_depth``, ``consistency_check``, ``save_ply`` (a file name): the value and geometry outputs of the module docstring.
+    ``save_confidence``, ``min_confidence`` (with ``save_ply``), ``peak_radius``: the plane sweep's confidence, taken in the forward's
+    own matching launch (``forward_with_depth_confidence`` / ``forward_sequence(return_confidence=True)``)."""
+    from .confidence import confidence_to_image, confidence_to_image_size
     from .io import write_png8
     from .prepost import InferenceGeometry
+    if min_confidence is not None and not save_ply:
+        raise ValueError('min_confidence filters the point cloud: it needs save_ply')
+    want_conf = bool(save_confidence) or min_confidence is not None
     imgs, poses, k = read_scene(scene_dir)
     os.makedirs(out_dir, exist_ok=True)
     collect = None
     if save_depth or consistency_check or save_ply:
         collect = _SceneCollector(out_dir, imgs, poses, k, save_depth, consistency_check, save_ply, int(ply_stride), int(min_views),
-                                  float(px_thr), float(rel_thr))
+                                  float(px_thr), float(rel_thr), None if min_confidence is None else float(min_confidence))
     skip = ('task', 'min_depth', 'max_depth', 'num_depth_candidates', 'depth_from_argmax', 'pred_bidir_depth', 'intrinsics', 'pose',
             'poses')
     fwd_kw = {key: v for key, v in fwd_kw.items() if key not in skip}
     if pairs_per_launch is not None:
         return _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, inference_size, min_depth, max_depth,
                                    num_depth_candidates, depth_from_argmax, pred_bidir_depth, scale_intrinsics, device,
-                                   int(pairs_per_launch), collect)
+                                   int(pairs_per_launch), collect, bool(save_confidence), want_conf, int(peak_radius))
     for i in range(len(imgs) - 1):
         ref, tgt = read_frame_u8(imgs[i])[None].to(device), read_frame_u8(imgs[i + 1])[None].to(device)
         size = tuple(inference_size) if inference_size else nearest_size(ref.shape[1:3], padding_factor)
@@ -137,28 +157,43 @@ def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_si
         if scale_intrinsics:
             intrinsics = InferenceGeometry.resized(ref.shape[1:3], size).scaled_intrinsics(intrinsics)
         pose = torch.from_numpy(relative_pose(poses[i], poses[i + 1]))[None].to(device)
+        depth_kw = dict(task='depth', intrinsics=intrinsics, pose=pose, min_depth=1. / max_depth, max_depth=1. / min_depth,
+                        num_depth_candidates=num_depth_candidates, depth_from_argmax=depth_from_argmax, pred_bidir_depth=pred_bidir_depth,
+                        **fwd_kw)
+        peak = None
         with torch.no_grad():
-            depth = model.predict(ref, tgt, inference_size=size, task='depth', intrinsics=intrinsics, pose=pose,
-                                  min_depth=1. / max_depth, max_depth=1. / min_depth, num_depth_candidates=num_depth_candidates,
-                                  depth_from_argmax=depth_from_argmax, pred_bidir_depth=pred_bidir_depth, **fwd_kw)['flow_preds'][-1]
+            if want_conf:                      # predict()'s steps around the forward that also returns the statistics
+                geom = InferenceGeometry.resized(ref.shape[1:3], size)
+                a0, a1 = geom.prepare(ref, tgt, normalize=True)
+                out = model.forward_with_depth_confidence(a0, a1, peak_radius=int(peak_radius), **depth_kw)
+                depth = geom.restore(out['flow_preds'][-1], 'depth')
+                conf = out['depth_confidence']
+                if min_confidence is not None:
+                    peak = confidence_to_image_size(conf['peak_mass'], conf['scale'], geom)
+            else:
+                depth = model.predict(ref, tgt, inference_size=size, **depth_kw)['flow_preds'][-1]
         rgb = inverse_depth_to_image(depth).cpu().numpy()                                    # [1 or 2, H, W, 3]
         stem = os.path.join(out_dir, os.path.splitext(os.path.basename(imgs[i]))[0])
         write_png8(stem + '.png', rgb[0])
         if pred_bidir_depth:
             write_png8(stem + '_bwd.png', rgb[1])
+        if save_confidence:
+            write_png8(stem + '_conf.png', confidence_to_image(conf['max_prob'][:1], tuple(ref.shape[1:3])).cpu().numpy()[0])
         if collect is not None:
-            collect.add(i, depth[0], ref[0])
+            collect.add(i, depth[0], ref[0], None if peak is None else peak[0])
             if pred_bidir_depth and i == len(imgs) - 2:
-                collect.add(i + 1, depth[1], tgt[0])
+                collect.add(i + 1, depth[1], tgt[0], None if peak is None else peak[1])
     if collect is not None:
         collect.finish()
     return max(0, len(imgs) - 1)
 
 
 def _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, inference_size, min_depth, max_depth,
-                        num_depth_candidates, depth_from_argmax, pred_bidir_depth, scale_intrinsics, device, step, collect=None):
+                        num_depth_candidates, depth_from_argmax, pred_bidir_depth, scale_intrinsics, device, step, collect=None,
+                        save_confidence=False, want_conf=False, peak_radius=1):
     """The scene through ``forward_sequence(task='depth')`` in pieces of ``step`` pairs (``step + 1`` frames first, then ``step`` frames
     joined by the carry), so that at most ``step + 1`` frames and their predictions are resident."""
+    from .confidence import confidence_to_image, confidence_to_image_size
     from .io import write_png8
     from .prepost import InferenceGeometry
     if step < 1:
@@ -188,7 +223,8 @@ def _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, 
             out = model.forward_sequence(frames, task='depth', intrinsics=intrinsics, poses=pose_dev[lo:hi], carry=carry,
                                          pairs_per_launch=step, min_depth=1. / max_depth, max_depth=1. / min_depth,
                                          num_depth_candidates=num_depth_candidates, depth_from_argmax=depth_from_argmax,
-                                         pred_bidir_depth=pred_bidir_depth, **fwd_kw)
+                                         pred_bidir_depth=pred_bidir_depth, return_confidence=want_conf, peak_radius=peak_radius,
+                                         **fwd_kw)
         carry = out['carry']
         first = lo - (0 if lo == 0 else 1)                                                   # the frame of the piece's first pair
         depth = [out['depth']] + ([out['depth_bwd']] if pred_bidir_depth else [])
@@ -200,13 +236,23 @@ def _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, 
             write_png8(stem + '.png', rgb[j])
             if pred_bidir_depth:
                 write_png8(stem + '_bwd.png', rgb[n + j])
+        peak = None
+        if want_conf:                                                                        # forward direction: the piece's n frames
+            conf = out['depth_confidence']
+            if save_confidence:
+                crgb = confidence_to_image(conf['max_prob'], shape[:2]).cpu().numpy()
+                for j in range(n):
+                    write_png8(os.path.join(out_dir, os.path.splitext(os.path.basename(imgs[first + j]))[0]) + '_conf.png', crgb[j])
+            if collect is not None and collect.min_confidence is not None:
+                peak = confidence_to_image_size(conf['peak_mass'], conf['scale'], geom)
         if collect is not None:
             # the frames of the piece's pairs: the carried frame starts the first pair of every piece but the first
             pending = frames_u8 if first == lo else torch.cat([pending, frames_u8], 0)
             for j in range(n):
-                collect.add(first + j, restored[j], pending[j])
+                collect.add(first + j, restored[j], pending[j], None if peak is None else peak[j])
             if pred_bidir_depth and hi == len(imgs):
-                collect.add(first + n, restored[2 * n - 1], pending[n])
+                # the sequence keeps the forward maps only: the last frame, seen backward, passes the confidence filter unfiltered
+                collect.add(first + n, restored[2 * n - 1], pending[n], None if peak is None else torch.ones_like(peak[0]))
             pending = pending[n:n + 1]                                                       # the last frame starts the next piece's first pair
         lo = hi
     if collect is not None:
@@ -236,6 +282,11 @@ def main(argv=None):
     ap.add_argument('--min-views', type=int, default=1, help='neighbouring frames (of two) that must agree with a pixel to keep it')
     ap.add_argument('--px-thr', type=float, default=1.0, help='round-trip reprojection error a consistent pixel stays below (pixels)')
     ap.add_argument('--rel-thr', type=float, default=0.01, help='relative depth error a consistent pixel stays below')
+    ap.add_argument('--save-confidence', action='store_true', help="write <stem>_conf.png: the plane sweep's max_prob, coloured")
+    ap.add_argument('--min-confidence', type=float, default=None, metavar='P',
+                    help='with --save-ply: keep a pixel only where the probability mass around its best depth candidate is >= P '
+                         '(with --pairs-per-launch and --pred-bidir-depth the last frame, seen backward, is not filtered on it)')
+    ap.add_argument('--peak-radius', type=int, default=1, metavar='R', help='candidates each side of the best one that count as its peak')
     ap.add_argument('--model-config', default='gmdepth_s1', choices=[k for k, v in CONFIGS.items() if v[1].get('task') == 'depth'])
     ap.add_argument('--weights', default=None, help="checkpoint (the reference's: a state_dict, or {'model': state_dict}); "
                                                     'default: the seeded synthetic weights')
@@ -247,7 +298,8 @@ def main(argv=None):
                   depth_from_argmax=args.depth_from_argmax, pred_bidir_depth=args.pred_bidir_depth,
                   scale_intrinsics=args.scale_intrinsics, pairs_per_launch=args.pairs_per_launch, save_depth=args.save_depth,
                   consistency_check=args.consistency_check, save_ply=args.save_ply, ply_stride=args.ply_stride, min_views=args.min_views,
-                  px_thr=args.px_thr, rel_thr=args.rel_thr)
+                  px_thr=args.px_thr, rel_thr=args.rel_thr, save_confidence=args.save_confidence, min_confidence=args.min_confidence,
+                  peak_radius=args.peak_radius)
     print(f'{n} frames written to {args.out}')
 
 

@@ -263,7 +263,8 @@ def back_project_points(depth, intrinsics, poses, keep=None, colors=None, min_de
     return points_pack_host(depth.float(), _cam_pack(k, p, False), keep, colors, min_depth, max_depth, int(stride))
 
 
-def fuse_depth_sequence(depths, intrinsics, poses, colors=None, px_thr=1.0, rel_thr=0.01, min_views=1, **points_kw):
+def fuse_depth_sequence(depths, intrinsics, poses, colors=None, px_thr=1.0, rel_thr=0.01, min_views=1, confidence=None,
+                        min_confidence=0., **points_kw):
     """The consistency-filtered world point cloud of a posed video: ``dict(xyz [N, 3], rgb [N, 3] or None, keep [T, H, W])``.
 
     ``depths [T, H, W]`` metric, ``intrinsics [1 or T, 3, 3]`` (row ``t`` serves both views of the pair ``(t, t + 1)``),
@@ -271,13 +272,17 @@ def fuse_depth_sequence(depths, intrinsics, poses, colors=None, px_thr=1.0, rel_
     frame, ``t - 1`` and ``t + 1``; ``keep[t]`` is 1 where at least ``min_views`` of its neighbours are consistent (the first and the
     last frame have one neighbour: ``min_views=2`` drops them).  All ``2 (T - 1)`` directed checks are one launch; the relative poses
     come from ``um_relative_pose_pairs`` and one bidirectional camera pack supplies the forward records and, rotated by ``T - 1``, the
-    inverse ones.  ``points_kw``: ``min_depth``, ``max_depth``, ``stride`` of :func:`back_project_points`, whose one synchronisation is
+    inverse ones.  ``confidence [T, H, W]`` (at the depths' size, e.g. the plane sweep's ``peak_mass`` brought to image size by
+    ``confidence.confidence_to_image_size``): ``keep`` is additionally 0 where ``confidence < min_confidence`` -- the one filter that
+    also serves a frame without a consistent neighbour; without it the result is unchanged.  ``points_kw``: ``min_depth``, ``max_depth``, ``stride`` of :func:`back_project_points`, whose one synchronisation is
     the only one here."""
     if depths.dim() != 3 or depths.shape[0] < 2:
         raise ValueError(f'expected depths [T >= 2, H, W], got {tuple(depths.shape)}')
     t = depths.shape[0]
     what = 'fuse_depth_sequence'
-    _same_device(what, depths, intrinsics=intrinsics, poses=poses, colors=colors)
+    _same_device(what, depths, intrinsics=intrinsics, poses=poses, colors=colors, confidence=confidence)
+    if confidence is not None and tuple(confidence.shape) != tuple(depths.shape):
+        raise ValueError(f'{what}: confidence {tuple(confidence.shape)} is not at the depths\' size {tuple(depths.shape)}')
     k, p = _expand_intrinsics(intrinsics, t, what), _check_poses(poses, t, what)
     depths = depths.float()
     ref, src = torch.cat([depths[:-1], depths[1:]], 0), torch.cat([depths[1:], depths[:-1]], 0)
@@ -292,5 +297,7 @@ def fuse_depth_sequence(depths, intrinsics, poses, colors=None, px_thr=1.0, rel_
     votes[:-1] += 1.0 - occ[:t - 1]                                    # frame t against t + 1
     votes[1:] += 1.0 - occ[t - 1:]                                     # frame t + 1 against t
     keep = (votes >= float(min_views)).float()
+    if confidence is not None:
+        keep = keep * (confidence >= float(min_confidence)).float()
     xyz, rgb = back_project_points(depths, k, p, keep=keep, colors=colors, **points_kw)
     return {'xyz': xyz, 'rgb': rgb, 'keep': keep}

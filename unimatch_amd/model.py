@@ -32,7 +32,7 @@ from .refine import BasicUpdateBlock, convex_upsample
 from .refine_nhwc import NhwcUpdateBlock
 from .dist import shard_batch, shard_bounds
 from .streams import PartRunner, forward_parts
-from .confidence import match_confidence
+from .confidence import depth_match_confidence, match_confidence
 
 _IMAGENET_MEAN = (0.485, 0.456, 0.406)
 _IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -492,7 +492,8 @@ class UniMatch(nn.Module):
         task = forward_kw.get('task', 'flow')
         if task == 'depth':
             raise NotImplementedError("forward_with_confidence: task='depth' matches by a plane sweep over depth candidates, which has "
-                                      "its own distribution; only 'flow' and 'stereo' have the global matching step")
+                                      "its own distribution; only 'flow' and 'stereo' have the global matching step "
+                                      "(forward_with_depth_confidence returns the statistics of the plane sweep's distribution)")
         if -1 not in (forward_kw.get('corr_radius_list') or ()):
             raise ValueError('forward_with_confidence needs a global matching step (a corr_radius of -1 in corr_radius_list)')
         if forward_kw.get('pred_bidir_flow') and task != 'flow':
@@ -500,6 +501,27 @@ class UniMatch(nn.Module):
         conf = {}
         out = dict(self._forward_batch(img0, img1, 1, confidence=conf, **forward_kw))
         out['match_confidence'] = conf
+        return out
+
+    def forward_with_depth_confidence(self, img0, img1, *, peak_radius=1, **forward_kw):
+        """:meth:`forward` for ``task='depth'`` plus ``'depth_confidence'``: statistics of the plane sweep's distribution over the
+        inverse-depth candidates of every feature pixel (the reference's ``match_prob``, unimatch/matching.py:227, which is never
+        formed).  A dict of ``max_prob``, ``entropy``, ``variance`` (about the soft-argmin, inverse depth squared), ``peak_mass`` (the
+        probability within ``peak_radius`` candidates of the best one) ``[B', h, w]`` float, ``best`` (first arg-max candidate) and
+        ``in_view`` (candidates that land inside the second view; 0: a uniform distribution) ``[B', h, w]`` int32, ``scale`` (the
+        map's stride in image pixels) and ``num_candidates``; ``B' = 2B`` with ``pred_bidir_depth`` (forward, then backward).  The
+        batch runs as one forward.  On the GPU the matching step is ONE launch (``um_depth_corr_softmax_stats``) that writes the
+        prediction and the statistics; on host tensors the prediction comes from the backend as in :meth:`forward` and the statistics
+        from ``confidence.depth_match_stats_host``."""
+        task = forward_kw.get('task', 'flow')
+        if task != 'depth':
+            raise ValueError(f"forward_with_depth_confidence: the plane sweep is the matching step of task='depth', got task={task!r} "
+                             "(forward_with_confidence serves 'flow' and 'stereo')")
+        if isinstance(peak_radius, bool) or not isinstance(peak_radius, int) or peak_radius < 0:
+            raise ValueError(f'peak_radius: expected an int >= 0, got {peak_radius!r}')
+        conf = {}
+        out = dict(self._forward_batch(img0, img1, 1, confidence=conf, peak_radius=peak_radius, **forward_kw))
+        out['depth_confidence'] = conf
         return out
 
     _PREDICT_DEFAULTS = {'flow': (8, 'sintel', 'flow'), 'stereo': (32, 'sintel', 'disparity'), 'depth': (16, 'kitti', 'depth')}
@@ -591,9 +613,10 @@ class UniMatch(nn.Module):
     def _forward_batch(self, img0, img1, parts, attn_type=None, attn_splits_list=None, corr_radius_list=None,
                        prop_radius_list=None, num_reg_refine=1, pred_bidir_flow=False, task='flow', intrinsics=None,
                        pose=None, min_depth=1. / 0.5, max_depth=1. / 10, num_depth_candidates=64,
-                       depth_from_argmax=False, pred_bidir_depth=False, confidence=None, **kwargs):
+                       depth_from_argmax=False, pred_bidir_depth=False, confidence=None, peak_radius=1, **kwargs):
         """:meth:`forward` with ``parts`` in place of ``launch_parts`` (``ConcurrentUniMatch`` forces its own count here).
-        ``confidence``: a dict the global matching step fills (:meth:`forward_with_confidence`; one part only)."""
+        ``confidence``: a dict the matching step fills (:meth:`forward_with_confidence`, :meth:`forward_with_depth_confidence` with
+        its ``peak_radius``; one part only)."""
         if self.training:
             raise RuntimeError('this module implements inference only: call .eval() '
                                '(training-mode auxiliary outputs of the reference are out of scope)')
@@ -605,7 +628,7 @@ class UniMatch(nn.Module):
         batch = img0.shape[0]
         parts = self._plan_parts(parts, task, attn_type, batch, img0.shape[-2], img0.shape[-1], img0.is_cuda)
         if parts <= 1:
-            return self._forward_one(img0, img1, confidence=confidence, **kw)
+            return self._forward_one(img0, img1, confidence=confidence, peak_radius=peak_radius, **kw)
         assert confidence is None, 'the matching confidence is collected by one forward of the whole batch'
 
         def prepare(r):
@@ -651,7 +674,7 @@ class UniMatch(nn.Module):
                          num_reg_refine=1, pred_bidir_flow=False, consistency_check=False, colorize=False, pairs_per_launch=8,
                          carry=None, task='flow', intrinsics=None, poses=None, min_depth=1. / 0.5, max_depth=1. / 10,
                          num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, track_points=None,
-                         return_confidence=False, interpolate=0):
+                         return_confidence=False, interpolate=0, peak_radius=1):
         """Optical flow of every pair (t, t+1) of a frame sequence ``frames [T, 3, H, W]`` (raw 0..255), each frame encoded ONCE.
 
         The reference's ``inference_flow`` (evaluate_flow.py:640-831) runs the model on each pair, so every interior frame goes through
@@ -693,7 +716,9 @@ class UniMatch(nn.Module):
         of :meth:`forward` unchanged; ``min_depth`` ... ``pred_bidir_depth`` mean what they mean there.  The carry also holds the last
         frame's pose and intrinsics row.  Returns ``{'depth': [P, H, W], 'carry': ...}``, plus ``'depth_bwd'`` (the depth of frame t + 1
         seen from pair t) with ``pred_bidir_depth`` and ``'depth_rgb'`` (``'depth_bwd_rgb'``) ``[P, H, W, 3]`` uint8 with ``colorize``
-        (``visualize.inverse_depth_to_image``).  On the GPU a depth call never waits for the device.  The depth keywords are ignored
+        (``visualize.inverse_depth_to_image``).  With ``return_confidence`` the result gains ``'depth_confidence'``, what
+        :meth:`forward_with_depth_confidence` returns (window ``peak_radius``), taken in the chunk's own plane-sweep launch: the maps
+        ``[P, h, w]`` of the forward direction, ``scale`` and ``num_candidates``; a chunk then runs as one part.  On the GPU a depth call never waits for the device.  The depth keywords are ignored
         for ``task='flow'``."""
         if self.training:
             raise RuntimeError('this module implements inference only: call .eval()')
@@ -704,20 +729,20 @@ class UniMatch(nn.Module):
             raise ValueError(f"task must be 'flow' or 'depth', got {task!r}")
         if task == 'depth' and track_points is not None:
             raise ValueError("track_points follows points through optical flow: it needs task='flow'")
-        if task == 'depth' and return_confidence:
-            raise NotImplementedError("return_confidence: task='depth' matches by a plane sweep, which has its own distribution")
+        if isinstance(peak_radius, bool) or not isinstance(peak_radius, int) or peak_radius < 0:
+            raise ValueError(f'peak_radius: expected an int >= 0, got {peak_radius!r}')
         if isinstance(interpolate, bool) or not isinstance(interpolate, int) or not 0 <= interpolate <= 16:
             raise ValueError(f'interpolate: expected an int in 0 .. 16 (in-between frames per pair), got {interpolate!r}')
         if interpolate and task == 'depth':
             raise ValueError("interpolate synthesises frames from optical flow: it needs task='flow'")
         if interpolate and not pred_bidir_flow:
             raise ValueError('interpolate needs pred_bidir_flow=True (the flows of both directions)')
-        if return_confidence and -1 not in (corr_radius_list or ()):
+        if return_confidence and task == 'flow' and -1 not in (corr_radius_list or ()):
             raise ValueError('return_confidence needs a global matching step (a corr_radius of -1 in corr_radius_list)')
         if task == 'depth':
             return self._depth_sequence(frames, attn_type, attn_splits_list, prop_radius_list, num_reg_refine, pred_bidir_flow,
                                         consistency_check, colorize, pairs_per_launch, carry, intrinsics, poses, min_depth, max_depth,
-                                        num_depth_candidates, depth_from_argmax, pred_bidir_depth)
+                                        num_depth_candidates, depth_from_argmax, pred_bidir_depth, return_confidence, peak_radius)
         self._check_bidir_flow(pred_bidir_flow)
         if consistency_check and not pred_bidir_flow:
             raise AssertionError('consistency_check needs pred_bidir_flow=True (as the reference asserts)')
@@ -835,7 +860,7 @@ class UniMatch(nn.Module):
 
     def _depth_sequence(self, frames, attn_type, attn_splits_list, prop_radius_list, num_reg_refine, pred_bidir_flow, consistency_check,
                         colorize, pairs_per_launch, carry, intrinsics, poses, min_depth, max_depth, num_depth_candidates,
-                        depth_from_argmax, pred_bidir_depth):
+                        depth_from_argmax, pred_bidir_depth, return_confidence=False, peak_radius=1):
         """:meth:`forward_sequence` for ``task='depth'`` (documented there).  Frame j of the call -- the carried frame first, when
         there is a carry -- has pose ``pose_all[j]`` and intrinsics ``k_all[j]``; pair j is frames (j, j + 1)."""
         # what forward (_forward_one) asserts for depth
@@ -877,6 +902,9 @@ class UniMatch(nn.Module):
         guard = torch.cuda.device(dev) if frames.is_cuda else contextlib.nullcontext()
         step = int(pairs_per_launch)
         out = {k: [] for k in ('depth', 'depth_bwd', 'depth_rgb', 'depth_bwd_rgb')}
+        confs = []                                        # per chunk: the plane sweep's confidence dict, forward direction
+        if return_confidence:
+            kw['peak_radius'] = peak_radius
         with guard, torch.no_grad():
             pose_all = poses.to(dev).float()
             k_all = intrinsics.to(dev).float().expand(count, 3, 3)
@@ -899,7 +927,10 @@ class UniMatch(nn.Module):
                 chunk = [([] if prev is None else [p]) + [f] for p, f in zip(prev or feats, feats)]
                 nb = new.shape[0] - (1 if prev is None else 0)
                 i += new.shape[0]
-                pred = self._match_pairs(chunk, nb, kw, k_all[done:done + nb], rel[done:done + nb])
+                conf = {} if return_confidence else None
+                pred = self._match_pairs(chunk, nb, kw, k_all[done:done + nb], rel[done:done + nb], confidence=conf)
+                if conf is not None:
+                    confs.append({k: v[:nb] if torch.is_tensor(v) else v for k, v in conf.items()})
                 done += nb
                 prev = [f[f.shape[0] - 1:] for f in feats]
                 fwd = pred[:nb]
@@ -913,6 +944,9 @@ class UniMatch(nn.Module):
                         out['depth_bwd_rgb'].append(visualize.inverse_depth_to_image(bwd))
             last = frames[frames.shape[0] - 1:]
             result = {k: v[0] if len(v) == 1 else torch.cat(v, 0) for k, v in out.items() if v}
+            if confs:
+                result['depth_confidence'] = {k: torch.cat([c[k] for c in confs], 0) if torch.is_tensor(confs[0][k]) else confs[0][k]
+                                              for k in confs[0]}
             result['carry'] = {'features': [p.clone() for p in prev], 'frame': last.clone(), 'state': self._carry_state(frames),
                                'pose': pose_all[-1:].clone(), 'intrinsics': k_all[-1:].clone()}
         return result
@@ -960,7 +994,7 @@ class UniMatch(nn.Module):
     def _forward_one(self, img0, img1, attn_type=None, attn_splits_list=None, corr_radius_list=None,
                      prop_radius_list=None, num_reg_refine=1, pred_bidir_flow=False, task='flow', intrinsics=None,
                      pose=None, min_depth=1. / 0.5, max_depth=1. / 10, num_depth_candidates=64,
-                     depth_from_argmax=False, pred_bidir_depth=False, pred_out=None, confidence=None):
+                     depth_from_argmax=False, pred_bidir_depth=False, pred_out=None, confidence=None, peak_radius=1):
         """One forward of the given samples on the current stream.  ``pred_out``: a contiguous ``[B, 2, H, W]`` tensor the flow
         prediction may be written to (it is then the returned prediction; a path that cannot do so ignores it)."""
         self._check_bidir_flow(pred_bidir_flow)
@@ -1002,7 +1036,7 @@ class UniMatch(nn.Module):
                                corr_radius_list=corr_radius_list, prop_radius_list=prop_radius_list, num_reg_refine=num_reg_refine,
                                pred_bidir_flow=pred_bidir_flow, task=task, intrinsics=intrinsics, pose=pose, min_depth=min_depth,
                                max_depth=max_depth, num_depth_candidates=num_depth_candidates, depth_from_argmax=depth_from_argmax,
-                               pred_bidir_depth=pred_bidir_depth, confidence=confidence)
+                               pred_bidir_depth=pred_bidir_depth, confidence=confidence, peak_radius=peak_radius)
 
     def _encode(self, images, task='flow', position=None):
         """The encode step: the CNN encoder of the images of the tuple ``images``, stacked in that order -> per-scale feature maps
@@ -1030,11 +1064,12 @@ class UniMatch(nn.Module):
     def _match(self, feats, nb, attn_type='', attn_splits_list=None, corr_radius_list=None, prop_radius_list=None, num_reg_refine=1,
                pred_bidir_flow=False, task='flow', intrinsics=None, pose=None, min_depth=1. / 0.5, max_depth=1. / 10,
                num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, stream_has_pos=False, pred_out=None,
-               confidence=None):
+               confidence=None, peak_radius=1):
         """The match step: everything after the encoder, on per-scale features ``feats[s] = [f0; f1]`` (``[2 nb, C, h, w]``, the
         first images of the ``nb`` pairs, then the second ones).  ``stream_has_pos``: the encoder added the position table already
         (``_forward_one`` decides; one scale, no refinement).  ``pred_out``: see ``_forward_one``.  ``confidence``: a dict that receives
-        ``confidence.match_confidence`` of the tokens the global matching step (``corr_radius == -1``) matches."""
+        ``confidence.match_confidence`` of the tokens the global matching step (``corr_radius == -1``) matches or, for depth,
+        ``confidence.depth_match_confidence`` of the plane sweep (window ``peak_radius``), whose launch then also writes the prediction."""
         ops = self.ops
         dev = feats[0].device
         flow, pred = None, None
@@ -1094,7 +1129,11 @@ class UniMatch(nn.Module):
                         pc = torch.cat([pose, torch.inverse(pose)], 0)
                     cam = torch.cat([torch.inverse(kc).flatten(1), pc[:, :3, :3].flatten(1), pc[:, :3, 3],
                                      kc.flatten(1)], 1).float().contiguous()
-                flow_pred = ops.depth_corr_softmax(f0c, f1c, h, w, cam, cand.contiguous(), depth_from_argmax)
+                if confidence is not None:
+                    flow_pred, conf = depth_match_confidence(ops, f0c, f1c, h, w, cam, cand.contiguous(), depth_from_argmax, up, peak_radius)
+                    confidence.update(conf)
+                else:
+                    flow_pred = ops.depth_corr_softmax(f0c, f1c, h, w, cam, cand.contiguous(), depth_from_argmax)
             else:
                 radius = corr_radius_list[s]
                 if radius == -1:

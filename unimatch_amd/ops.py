@@ -1452,8 +1452,13 @@ class HipOps(WorkspaceRegistry):
         _abi.check(code, 'um_prop_local_attn')
         return out
 
-    def depth_corr_softmax(self, f0, f1, h, w, cam, candidates, from_argmax=False):
-        """cam ``[B, 30]`` = K^-1 | R | t | K (row major), candidates ``[D]`` inverse depths."""
+    def depth_corr_softmax(self, f0, f1, h, w, cam, candidates, from_argmax=False, stats=False, peak_radius=1):
+        """cam ``[B, 30]`` = K^-1 | R | t | K (row major), candidates ``[D]`` inverse depths -> ``out [B, 1, h, w]``.
+
+        ``stats=True``: the same sweep as ONE ``um_depth_corr_softmax_stats`` launch (recorded as ``'depth_corr_softmax_stats'``) that
+        also writes the statistics of the distribution it reduces -> ``(out, stats [B, 4, h, w] = max_prob | entropy | variance |
+        peak_mass, index [B, 2, h, w] int32 = best | in_view)``; ``peak_radius``: candidates each side of the best one that count
+        towards ``peak_mass``.  Its memory-contract cases are in tests/test_depth_stats_gpu.py."""
         b, l, c = f0.shape
         _check_tokens('f0', f0, tokens=h * w)
         _check_tokens('f1', f1, b, l)
@@ -1463,6 +1468,14 @@ class HipOps(WorkspaceRegistry):
                 and candidates.dim() == 1):
             raise ValueError('candidates: expected contiguous CUDA float32 [D]')
         out = torch.empty((b, 1, h, w), dtype=torch.float32, device=f0.device)
+        if stats:
+            planes = torch.empty((b, 4, h, w), dtype=torch.float32, device=f0.device)
+            index = torch.empty((b, 2, h, w), dtype=torch.int32, device=f0.device)
+            code = self._launch('depth_corr_softmax_stats', lambda: self.lib.um_depth_corr_softmax_stats(
+                _ptr(f0), _ptr(f1), _ptr(cam), _ptr(candidates), _ptr(out), _ptr(planes), _ptr(index), b, h, w, c,
+                candidates.numel(), int(bool(from_argmax)), int(peak_radius), _stream()))
+            _abi.check(code, 'um_depth_corr_softmax_stats')
+            return out, planes, index
         code = self._launch('depth_corr_softmax', lambda: self.lib.um_depth_corr_softmax(
             _ptr(f0), _ptr(f1), _ptr(cam), _ptr(candidates), _ptr(out), b, h, w, c,
             candidates.numel(), int(bool(from_argmax)), _stream()))
