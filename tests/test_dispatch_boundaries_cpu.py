@@ -1,0 +1,216 @@
+"""The host side of the kernel-selection rules, without a GPU: the exported plan / split / part-count functions on both sides of every
+switch, the Python restatements tests/dispatch_boundaries.py uses against the library's answers, the refusals one step beyond the
+advertised tap and candidate range (decided on the host before any HIP call), and the conditioning of the arg-max read-out's inputs.
+Without a device the library's CU count is its fallback of 256 (common.h:19-28); every assertion below holds for any count."""
+import ctypes
+
+import pytest
+import torch
+
+from tests import dispatch_boundaries as db
+from unimatch_amd import _abi
+
+
+@pytest.fixture(scope='module')
+def lib():
+    return _abi.load()
+
+
+def _cus(lib):
+    """The CU count the plan functions use, recovered from the FFN rule: the largest tile count that still splits in two is CUs / 2."""
+    steps = db.ffn_split_steps(lib, 1024)
+    assert steps and steps[-1][2:] == (2, 1), steps
+    return 2 * (steps[-1][0] // 128)
+
+
+# ------------------------------------------------------------------ window attention: token table and key split
+def test_token_table_holds_windows_of_2048_tokens():
+    """window_attn.hip:231.  The geometries of row 1 of the GPU file sit where they are meant to."""
+    assert db.attn_uses_token_table(32, 64) and not db.attn_uses_token_table(1, 2080) and not db.attn_uses_token_table(40, 52)
+    assert not db.attn_uses_token_table(33, 64) and db.attn_uses_token_table(1, 2048) and not db.attn_uses_token_table(1, 2049)
+
+
+def test_key_split_needs_eight_and_sixteen_key_tiles(lib):
+    """window_attn.hip:1100 -- ``ntiles >= 4 * (2 * split)``: one window of 7 key tiles (224 tokens) stays whole, 8 (256 tokens) splits in
+    two, 15 (480) stays at two, 16 (512) splits in four -- on any device with at least 16 CUs."""
+    assert db.attn_plan(lib, 1, 14, 16, 14, 16) == (2, 0, 1)
+    assert db.attn_plan(lib, 1, 16, 16, 16, 16) == (0, 2, 2)
+    assert db.attn_plan(lib, 1, 15, 32, 15, 32) == (0, 4, 2)
+    assert db.attn_plan(lib, 1, 16, 32, 16, 32) == (0, 4, 4)
+    assert lib.um_window_attn_ksplit_workspace_bytes(1, 14, 16, 14, 16) == 0
+    assert lib.um_window_attn_ksplit_workspace_bytes(1, 16, 16, 16, 16) == 256 + 2 * 2 * 17 * 256 * 4 * 4     # window_attn.hip:1132
+
+
+def test_key_split_steps_follow_the_cu_count(lib):
+    """window_attn.hip:1100, 1125 -- ``total * 2 * split <= 2 * CUs``: stacking 512-token windows, the launch goes from 4 parts to 2
+    when its tiles pass CUs / 2 and from 2 to 1 when they pass CUs, and the restated rule agrees with the library at every count."""
+    cus = _cus(lib)
+    steps = db.attn_split_steps(lib)
+    assert [s[2:] for s in steps] == [(4, 2), (2, 1)], steps
+    assert 4 * steps[0][0] <= cus // 2 < 4 * steps[0][1] and 4 * steps[1][0] <= cus < 4 * steps[1][1], (steps, cus)
+    wh, ww = db.STEP_WINDOW
+    for k in range(1, 200):
+        assert db.attn_parts(lib, 1, wh * k, ww, wh, ww) == db.attn_split_rule(4 * k, 16, cus), k
+    # the 2112-token shifted geometry of row 1: 17 query tiles x 4 windows, 66 key tiles
+    for s in (1, 2, 3, 4, 8):
+        assert db.attn_parts(lib, s, 66, 128, 33, 64) == db.attn_split_rule(68 * s, 66, cus), s
+    assert db.attn_parts(lib, db.attn_unsplit_streams(lib, 66, 128, 33, 64), 66, 128, 33, 64) == 1
+
+
+def test_plan_rejects_bad_geometry(lib):
+    f = ctypes.c_int()
+    assert lib.um_window_attn_plan(1, 10, 10, 3, 5, ctypes.byref(f), ctypes.byref(f), ctypes.byref(f)) == db.UM_ERR_BAD_ARG
+    assert lib.um_window_attn_plan(1, 10, 10, 5, 5, None, ctypes.byref(f), ctypes.byref(f)) == db.UM_ERR_BAD_ARG
+    assert lib.um_window_attn_ksplit_workspace_bytes(1, 10, 10, 3, 5) == 0
+
+
+# ------------------------------------------------------------------ FFN hidden split
+def test_ffn_split_steps_follow_the_cu_count(lib):
+    """ffn.hip:983 -- ``tiles * 2 * split <= CUs`` at hidden 1024 (32 slices: no slice condition binds): 4 parts up to CUs / 4 tiles,
+    2 up to CUs / 2, then none; the byte count is the closed form of ffn.hip:987-990."""
+    cus = _cus(lib)
+    steps = db.ffn_split_steps(lib, 1024)
+    assert [s[2:] for s in steps] == [(4, 2), (2, 1)], steps
+    assert steps[0][0] == 128 * (cus // 4) and steps[1][0] == 128 * (cus // 2), (steps, cus)
+    for m in (1, 128, 129, steps[0][0], steps[0][1], steps[1][0], steps[1][1], 100000):
+        assert db.ffn_split(lib, m, 1024) == db.ffn_split_rule(m, 1024, cus), m
+    if cus == 256:
+        assert [s[:2] for s in steps] == [(8192, 8193), (16384, 16385)]
+    m = steps[0][0]
+    assert lib.um_ffn_split_workspace_bytes(m, 1024) == (m // 128 * 4 + 255) // 256 * 256 + m // 128 * 4 * 64 * 256 * 4
+
+
+def test_ffn_split_slice_conditions(lib):
+    """ffn.hip:983 -- ``nslice % (2 * split) == 0 && nslice / (2 * split) >= 4`` at one tile: 2, 3 and 4 slices do not split, 8 split in
+    two (4 per part; 2 per part would be too few for four), 10 split in two (an odd 5 per part cannot halve again), 16 split in four."""
+    want = {64: 1, 96: 1, 128: 1, 224: 1, 256: 2, 320: 2, 384: 2, 512: 4, 1024: 4}
+    cus = _cus(lib)
+    for hidden, split in want.items():
+        assert db.ffn_split(lib, 128, hidden) == split == db.ffn_split_rule(128, hidden, cus), hidden
+    assert lib.um_ffn_split_workspace_bytes(128, 48) == 0 and lib.um_ffn_split_workspace_bytes(0, 1024) == 0      # not served at all
+
+
+# ------------------------------------------------------------------ local family: grid cap, tap range, refusals
+def test_pixel_grid_cap_is_16384_pixels():
+    """local_ops.hip:762-767."""
+    assert db.pixel_grid_trips(128 * 128) == 1 and db.pixel_grid_trips(129 * 128) == 2 and db.pixel_grid_trips(1) == 1
+    assert db.pixel_grid_trips((2 * 363 * 362 + 15) // 16) == 2 and db.pixel_grid_trips(262144 // 16) == 1   # K4: blocks of 16 pixels
+
+
+def _buffers():
+    """Pointers for calls that must be refused before any HIP call.  Without a device they are fake and non-null -- a call that was
+    let through returns a positive HIP error.  With a device they are real and large enough for the geometry asked for, so that a
+    call that was let through is a failed assertion and nothing else."""
+    if torch.cuda.is_available():
+        keep = [torch.zeros(1 << 18, dtype=torch.float32, device='cuda') for _ in range(7)]
+        return keep, [t.data_ptr() for t in keep]
+    return None, [0x1000 * (i + 1) for i in range(7)]
+
+
+def test_refusals_beyond_the_tap_range_are_decided_on_the_host(lib):
+    """One step beyond LOCAL_MAX_ROUNDS x 16 = 128 taps / candidates (local_ops.hip:773, 892, 906, 931) and beyond the cost volume's 81
+    taps (:791, :874): UM_ERR_UNSUPPORTED and a message, on 8 x 8 maps."""
+    keep, (a, b, c, d, e, f, g) = _buffers()
+    lib.um_census_enable(1)
+    calls = {
+        '2-D radius 6 (169 taps)': lambda: lib.um_local_corr_softmax(a, b, c, 1, 8, 8, 128, 6, 0, None),
+        '1-D radius 64 (129 taps)': lambda: lib.um_local_corr_softmax(a, b, c, 1, 8, 8, 128, 64, 1, None),
+        'prop_local radius 6': lambda: lib.um_prop_local_attn(a, b, c, d, 1, 8, 8, 128, 2, 6, None),
+        '129 candidates': lambda: lib.um_depth_corr_softmax(a, b, c, d, e, 1, 8, 8, 128, 129, 0, None),
+        '129 candidates, stats': lambda: lib.um_depth_corr_softmax_stats(a, b, c, d, e, f, g, 1, 8, 8, 128, 129, 0, 1, None),
+        'no candidate': lambda: lib.um_depth_corr_softmax(a, b, c, d, e, 1, 8, 8, 128, 0, 0, None),
+        'cost volume radius 5 (121 taps)': lambda: lib.um_local_corr_with_flow(a, b, c, d, 1, 8, 8, 128, 5, None),
+        'dilated cost volume radius 5': lambda: lib.um_local_corr_with_flow_dilated(a, b, c, d, 1, 8, 8, 128, 5, 2, None),
+    }
+    for what, call in calls.items():
+        rc = call()
+        assert rc == db.UM_ERR_UNSUPPORTED, (what, rc)
+        assert lib.um_last_error_string(), what
+    assert all(v == 0 for v in _abi.census(lib).values())                  # no launch was counted
+    lib.um_census_enable(0)
+    del keep
+
+
+def test_the_last_served_tap_counts():
+    """What row 5 of the GPU file runs is inside the range: 2-D radius 5 = 121 taps, 1-D radius 63 = 127, 128 candidates."""
+    assert 11 * 11 <= db.LOCAL_MAX_TAPS < 13 * 13 and 2 * 63 + 1 <= db.LOCAL_MAX_TAPS < 2 * 64 + 1
+    assert 9 * 9 <= db.K4_MAX_TAPS < 11 * 11
+    assert db.depth_uses_box_kernel(64) and not db.depth_uses_box_kernel(65)
+
+
+@pytest.mark.parametrize('nd', db.SWEEP_COUNTS)
+def test_argmax_inputs_are_well_conditioned_in_fp32(nd):
+    """The arg-max read-out is gated by "at most 1 % of the pixels differ by more than 1e-6" from the fp64 oracle.  That gate is only
+    fair where fp32 arithmetic itself decides the arg-max as fp64 does: for the candidates and features of row 5, the fp32 evaluation
+    of the same oracle stays within that 1 %."""
+    b, h, w = db.SWEEP_SMALL
+    want = db.sweep_reference(b, h, w, nd, True)
+    f32 = db.sweep_reference(b, h, w, nd, True, torch.float32)
+    differ = (f32.double() - want).abs().gt(1e-6).float().mean().item()
+    assert differ < 0.01, (nd, differ)
+
+
+# ------------------------------------------------------------------ conv_pick
+PICK = [
+    # hi, wi, cout, kh, kw, stride, ph, pw -> kind            conv.hip:1199: the row-window kernel needs ho * wo >= 256
+    ((15, 17, 64, 3, 3, 1, 1, 1), 'generic'), ((16, 16, 64, 3, 3, 1, 1, 1), 'rows'),
+    # conv.hip:1203: the patch kernel needs 4 ho wo >= 3 x the area of its 8 x 32 tiles
+    ((17, 33, 64, 3, 3, 1, 1, 1), 'rows'), ((24, 32, 64, 3, 3, 1, 1, 1), 'patch'),
+    ((5, 64, 64, 3, 3, 1, 1, 1), 'rows'), ((6, 64, 64, 3, 3, 1, 1, 1), 'patch'),          # ragged in rows only: 5/8 | 6/8 of a tile
+    ((8, 47, 64, 3, 3, 1, 1, 1), 'rows'), ((8, 48, 64, 3, 3, 1, 1, 1), 'patch'),          # ragged in columns only: 47/64 | 48/64
+    # conv.hip:1200: five-tap rows on 128-wide tiles only
+    ((16, 16, 128, 1, 5, 1, 0, 2), 'rows'), ((16, 16, 96, 1, 5, 1, 0, 2), 'generic'),
+    ((16, 16, 128, 5, 1, 1, 2, 0), 'generic'), ((16, 16, 96, 5, 1, 1, 2, 0), 'generic'),
+    ((16, 32, 64, 3, 3, 2, 1, 1), 'generic'), ((16, 32, 64, 3, 3, 1, 0, 0), 'generic'),
+]
+WIDTHS = {4: 2, 32: 2, 36: 2, 64: 2, 96: 3, 128: 4, 160: 4, 192: 3, 200: 4, 256: 4}           # conv.hip:1191
+
+
+def test_conv_pick_restated_agrees_with_the_library(lib):
+    """conv.hip:1189-1250.  um_conv_stats_parts and um_conv2d_norm_supported are the library's own reading of conv_pick: the part count
+    is the patch kernel's ``2 x tiles`` exactly where the restated rule says 'patch', and the on-load kernel is offered there and only
+    there (for tile widths of at least 64 columns)."""
+    for geo, kind in PICK:
+        hi, wi, cout, kh, kw, stride, ph, pw = geo
+        got, nt = db.conv_kind(*geo)
+        assert got == kind, (geo, got)
+        ho, wo = (hi + 2 * ph - kh) // stride + 1, (wi + 2 * pw - kw) // stride + 1
+        assert lib.um_conv_stats_parts(*geo) == db.conv_parts(kind, ho, wo), geo
+        assert lib.um_conv2d_norm_supported(hi, wi, 64, cout, kh, kw, stride, ph, pw, 0) == int(kind == 'patch'), geo
+    assert {c: db.conv_tile_width(c) for c in WIDTHS} == WIDTHS
+    for cout, nt in WIDTHS.items():
+        assert db.conv_kind(16, 32, cout, 3, 3, 1, 1, 1) == ('patch', 1 if cout <= 32 else nt)
+        assert db.conv_kind(9, 11, cout, 3, 3, 1, 1, 1) == ('generic', nt)
+        # conv.hip:1205, 1224: a head of up to 32 outputs takes the 32-wide tile, which has no on-load form
+        assert lib.um_conv2d_norm_supported(16, 32, 64, cout, 3, 3, 1, 1, 1, 0) == int(cout > 32), cout
+        assert lib.um_conv2d_norm_supported(9, 11, 64, cout, 3, 3, 1, 1, 1, 0) == 0
+    # the 3/4 rule tells the two part counts apart wherever they differ: the sweep of every size up to 40 x 70
+    for hi in range(1, 41):
+        for wi in range(1, 71):
+            kind, _ = db.conv_kind(hi, wi, 64, 3, 3, 1, 1, 1)
+            assert lib.um_conv_stats_parts(hi, wi, 64, 3, 3, 1, 1, 1) == db.conv_parts(kind, hi, wi), (hi, wi)
+            assert lib.um_conv2d_norm_supported(hi, wi, 64, 64, 3, 3, 1, 1, 1, 0) == int(kind == 'patch'), (hi, wi)
+
+
+def test_entry_kernel_conditions(lib):
+    """conv.hip:1232-1241: 3x3 / stride 2 / pad 1, at most 128 input channels, 96- and 128-wide output tiles."""
+    ok = lib.um_conv2d_entry_supported
+    assert ok(17, 33, 128, 128, 3, 3, 2, 1, 1, 0) == 1 and ok(17, 33, 160, 128, 3, 3, 2, 1, 1, 0) == 0       # cin 128 | 160
+    assert ok(17, 33, 64, 96, 3, 3, 2, 1, 1, 0) == 1 and ok(17, 33, 64, 64, 3, 3, 2, 1, 1, 0) == 0           # NT 3 | 2
+    assert ok(17, 33, 96, 192, 3, 3, 2, 1, 1, 0) == 1 and ok(17, 33, 96, 200, 3, 3, 2, 1, 1, 0) == 1         # NT 3 | 4
+    assert ok(17, 33, 64, 96, 3, 3, 1, 1, 1, 0) == 0 and ok(17, 33, 64, 96, 5, 5, 2, 2, 2, 0) == 0
+    assert ok(17, 33, 64, 96, 3, 3, 2, 0, 0, 0) == 0 and ok(17, 33, 48, 96, 3, 3, 2, 1, 1, 0) == 0
+
+
+def test_convolution_refuses_two_output_channels_on_the_host(lib):
+    """The flow head's 256 -> 2 is served as a convolution padded to 4 outputs: ``cout % 4 != 0`` is a bad argument (conv.hip:1268)."""
+    keep, (a, b, c, d, e, f, g) = _buffers()
+    rc = lib.um_conv2d_fwd(a, b, None, c, None, 1, 8, 8, 32, 2, 3, 3, 1, 1, 1, 0, 10, 0, None)
+    assert rc == db.UM_ERR_BAD_ARG and lib.um_last_error_string()
+    del keep
+
+
+# ------------------------------------------------------------------ NHWC norm
+def test_norm_statistics_parts_of_the_gpu_rows():
+    """nhwc_ops.hip:15, 74-75: chunks of 256 pixels; up to 1024 parts stay in registers."""
+    assert 512 * 512 // db.NORM_CHUNK_ROWS == db.NORM_PARTS_IN_REGISTERS and 513 * 512 // db.NORM_CHUNK_ROWS == db.NORM_PARTS_IN_REGISTERS + 2

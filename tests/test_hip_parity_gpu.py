@@ -14,6 +14,7 @@ import torch
 
 from oracle import hotpath as hp
 from oracle import model as om
+from tests.dispatch_boundaries import merged_layer_reference
 from unimatch_amd import UniMatch
 from unimatch_amd.ops import HipOps
 from unimatch_amd.synth import CONDITIONED, CONFIGS, synth_camera, synth_images, synth_state_dict
@@ -1120,14 +1121,7 @@ def test_attention_merge_and_kv_rotate(ops, shifted, residual):
     geom = (8, 12, 4, 6) if shifted else (8, 12, 0, 0)
     rot = 2
     # fp64 reference: explicit rotation of the key / value streams, oracle attention, merge, LayerNorm
-    q64 = (x.double() @ wq.double().t()).view(s_, l, c)
-    kv_src = xt.double().view(s_, l, c).roll(-rot, 0)                       # stream s reads stream (s + rot) mod S
-    k64, v64 = kv_src @ wk.double().t(), kv_src @ wv.double().t()
-    att = hp.window_attention(q64, k64, v64, h, w, *geom)
-    want = torch.nn.functional.layer_norm(att.reshape(s_ * l, c) @ wm.double().t(), (c,), norm.weight.double(),
-                                          norm.bias.double(), norm.eps)
-    if residual:
-        want = want + x.double()
+    want = merged_layer_reference(x, xt, wq, wk, wv, wm, norm, s_, h, w, geom, rot, residual)
     norm = norm.to(DEV)
     xd, xtd = x.to(DEV), xt.to(DEV)
     qp, _, _ = ops.linear_planes(xd, (wq.to(DEV),))
