@@ -67,7 +67,8 @@ const char* um_last_error_string(void);
 #define UM_RANGE_ATTN_OUTPUT 8u   /* um_window_attn_*merge*_fwd: the attention output fed to the merge Linear                 */
 #define UM_RANGE_FFN_TOKENS 16u   /* um_ffn_*fwd: the concatenated input [x | y]                                              */
 #define UM_RANGE_FFN_HIDDEN 32u   /* ... the hidden activations gelu(W1.[x | y])                                              */
-#define UM_RANGE_KV_TOKENS 64u    /* um_kv4_fwd / the k | v epilogue of um_ffn_kv_fwd: tokens, and the projected keys / values */
+#define UM_RANGE_KV_TOKENS 64u    /* um_kv4_fwd / the k | v epilogue of um_ffn_kv_fwd: tokens, and the projected keys / values;
+                                     the token planes of um_ffn_planes_fwd                                                   */
 #define UM_RANGE_LINEAR 128u      /* um_linear_fwd: fp32 inputs and plane outputs                                             */
 int um_range_flags(unsigned* flags_out, int reset);
 
@@ -272,6 +273,14 @@ int um_kv4_fwd(const float* x, const void* wc_planes, int m, int wshift, void* o
 int um_ffn_kv_fwd(const float* x, const float* y, const void* w1_planes, const void* w2_planes, int m, int hidden, int wshift,
                   const float* gamma, const float* beta, float eps, float* out, const void* wc_planes, void* kv_planes, int mode,
                   void* workspace, size_t workspace_bytes, void* stream);
+/* um_ffn_ws_fwd AND the operand planes of its result from ONE launch: out_planes [NS][m][128] is bit for bit
+ * um_weight_planes(out, out_planes, m, 128, 0, mode) -- the hi | lo split of `out` at scale 1 -- written by the store loop that
+ * writes `out`.  With the k | v projections folded into the query and merge weights (q' = Wk^T Wq, merge' = Wm Wv: single head,
+ * bias-free, nothing non-linear between projection and attention) the token stream itself is the key / value operand of the next
+ * block's two attention launches.  Launches small enough for the hidden split run the format pass as a second launch inside the call. */
+int um_ffn_planes_fwd(const float* x, const float* y, const void* w1_planes, const void* w2_planes, int m, int hidden, int wshift,
+                      const float* gamma, const float* beta, float eps, float* out, void* out_planes, int mode, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Convolutions either side of the matching path, NHWC, on the matrix cores with the same

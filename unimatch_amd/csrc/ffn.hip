@@ -68,6 +68,9 @@ struct FfnArgs {
     // KV4 variant: the NEXT block's key / value projections of the tile this workgroup has just finished (kv4_project)
     Kv4Args kv;
     unsigned* range_flag;         // um_range_flags (as Kv4Args)
+    // PLANES variant: the normalised tile also leaves as operand planes [NS][M][128] (split_planes_kernel's result on `out`)
+    unsigned short* planes;
+    long planes_stride;           // M * 128
 };
 
 // Issue priority of the pair's two waves inside the MFMA stream.  The partners w and w + 4 share a SIMD and run
@@ -308,7 +311,10 @@ __global__ __launch_bounds__(512, 2) void kv4_kernel(Kv4Args k) {
     kv4_project<T, NS, false>(lds, lds + Kv4Lds<NS>::RING, k, yf, m0, wave, lane, aoff, neg1);
 }
 
-template <typename T, int NS, bool HSPLIT = false, bool KV4 = false>
+// PLANES: the rows the epilogue stores also leave as hi (| lo) operand planes -- with the k | v projections folded into the query and
+// merge weights (ops.py: HipOps.fold_kv) the token stream ITSELF is the next block's key / value operand, so the format pass that
+// would read `out` back is the store loop's second (third) store of the vector it already holds.
+template <typename T, int NS, bool HSPLIT = false, bool KV4 = false, bool PLANES = false>
 __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
     using L = FfnLds<NS>;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -880,13 +886,26 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(FfnArgs a) {
             }
         __builtin_amdgcn_wave_barrier();                            // same wave: LDS executes its accesses in order
         const int cc = lane & 31;
+        float pmx = 0.f;                                            // PLANES: largest element turned into an fp16 operand
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int r = 2 * j + half;
             const f32x4 v = *reinterpret_cast<const f32x4*>(stg + r * 512 + ((cc ^ r) << 4));
             const int trow = m0 + 32 * pair + r;
-            if (trow < a.M) *reinterpret_cast<f32x4*>(a.out + (long)trow * 128 + 4 * cc) = v;
+            if (trow < a.M) {
+                *reinterpret_cast<f32x4*>(a.out + (long)trow * 128 + 4 * cc) = v;
+                if constexpr (PLANES) {
+                    // the same split of the same fp32 values as split_planes_kernel (scale 1): a row of a plane is 32 lanes x 8 bytes
+                    pmx = fmaxf(fmaxf(pmx, fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1]))), fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3])));
+                    unsigned short* pp = a.planes + (long)trow * 128 + 4 * cc;
+                    const unsigned h0 = T::pack2(v[0], v[1]), h1 = T::pack2(v[2], v[3]);
+                    *reinterpret_cast<u32x2*>(pp) = u32x2{h0, h1};
+                    if (NS == 2)
+                        *reinterpret_cast<u32x2*>(pp + a.planes_stride) = u32x2{T::lo2(v[0], v[1], h0, neg1), T::lo2(v[2], v[3], h1, neg1)};
+                }
+            }
         }
+        if constexpr (PLANES) um_range_note<T>(a.range_flag, pmx, UM_RANGE_KV_TOKENS);
     }
 #ifdef UM_FFN_TRACE
     if (tracing) trace_buf[24 * 8 + 2] = __builtin_amdgcn_s_memtime();          // end of LayerNorm + residual + stores
@@ -949,26 +968,27 @@ extern "C" int um_debug_set_ffn_trace(void* ptr) {
 }
 #endif
 
-template <typename T, int NS, bool HSPLIT, bool KV4 = false>
+template <typename T, int NS, bool HSPLIT, bool KV4 = false, bool PLANES = false>
 static hipError_t launch_ffn_impl(const FfnArgs& a, hipStream_t stream) {
     // KV4: ring [0, 64 KB) + exchange / scratch [64 KB, 128 KB) -- the same 128 KB the main loop uses
     constexpr int LDS = FfnLds<NS>::TOTAL > 131072 ? FfnLds<NS>::TOTAL : (KV4 ? 131072 : FfnLds<NS>::TOTAL);
     static bool configured = false;          // opt in to > 64 KB of LDS once per instantiation
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_kernel<T, NS, HSPLIT, KV4>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_kernel<T, NS, HSPLIT, KV4, PLANES>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         if (e != hipSuccess) return e;
         configured = true;
     }
     ScopedKernelTimer timer(UM_K_FFN, stream);
     um_census_hit(HSPLIT ? UM_V_FFN_HSPLIT : UM_V_FFN_TILE);
-    hipLaunchKernelGGL((ffn_kernel<T, NS, HSPLIT, KV4>), dim3(((a.M + 127) / 128) * a.split), dim3(512), LDS, stream, a);
+    hipLaunchKernelGGL((ffn_kernel<T, NS, HSPLIT, KV4, PLANES>), dim3(((a.M + 127) / 128) * a.split), dim3(512), LDS, stream, a);
     return hipGetLastError();
 }
 
 template <typename T, int NS>
 static hipError_t launch_ffn(const FfnArgs& a, hipStream_t stream) {
     if (a.kv.w) return launch_ffn_impl<T, NS, false, true>(a, stream);       // (callers only set kv on un-split launches)
+    if (a.planes) return launch_ffn_impl<T, NS, false, false, true>(a, stream);   // (... and planes)
     return a.split > 1 ? launch_ffn_impl<T, NS, true>(a, stream) : launch_ffn_impl<T, NS, false>(a, stream);
 }
 
@@ -1008,13 +1028,13 @@ extern "C" int um_ffn_fwd(const float* x, const float* y, const void* w1_planes,
 extern "C" int um_kv4_fwd(const float* x, const void* wc_planes, int m, int wshift, void* out_planes, int mode, void* stream_);
 static int ffn_impl(const float* x, const float* y, const void* w1_planes, const void* w2_planes, int m, int hidden,
                     int wshift, const float* gamma, const float* beta, float eps, float* out, int mode, void* workspace,
-                    size_t workspace_bytes, const void* wc_planes, void* kv_planes, void* stream_);
+                    size_t workspace_bytes, const void* wc_planes, void* kv_planes, void* out_planes, void* stream_);
 
 extern "C" int um_ffn_ws_fwd(const float* x, const float* y, const void* w1_planes, const void* w2_planes, int m, int hidden,
                              int wshift, const float* gamma, const float* beta, float eps, float* out, int mode, void* workspace,
                              size_t workspace_bytes, void* stream_) {
     return ffn_impl(x, y, w1_planes, w2_planes, m, hidden, wshift, gamma, beta, eps, out, mode, workspace, workspace_bytes, nullptr,
-                    nullptr, stream_);
+                    nullptr, nullptr, stream_);
 }
 
 // The FFN of block i AND the key / value projections of block i + 1 (um_kv4_fwd's result on `out`) from one launch: the tile a
@@ -1028,12 +1048,27 @@ extern "C" int um_ffn_kv_fwd(const float* x, const float* y, const void* w1_plan
         return -1;
     }
     return ffn_impl(x, y, w1_planes, w2_planes, m, hidden, wshift, gamma, beta, eps, out, mode, workspace, workspace_bytes, wc_planes,
-                    kv_planes, stream_);
+                    kv_planes, nullptr, stream_);
+}
+
+// um_ffn_ws_fwd AND the operand planes of its result (um_weight_planes(out, ., m, 128, 0, mode): the hi | lo split at scale 1) from
+// ONE launch: the store loop of the epilogue writes every row it holds a second time as planes.  With the k | v projections folded
+// into the query and merge weights the stream itself is the next block's key / value operand.  Hidden-split launches keep the
+// FFN's split variant and run the format pass as a second launch inside the call: same bits either way.
+extern "C" int um_ffn_planes_fwd(const float* x, const float* y, const void* w1_planes, const void* w2_planes, int m, int hidden,
+                                 int wshift, const float* gamma, const float* beta, float eps, float* out, void* out_planes, int mode,
+                                 void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!out_planes) {
+        um_set_error("um_ffn_planes_fwd: null output planes");
+        return -1;
+    }
+    return ffn_impl(x, y, w1_planes, w2_planes, m, hidden, wshift, gamma, beta, eps, out, mode, workspace, workspace_bytes, nullptr,
+                    nullptr, out_planes, stream_);
 }
 
 static int ffn_impl(const float* x, const float* y, const void* w1_planes, const void* w2_planes, int m, int hidden,
                     int wshift, const float* gamma, const float* beta, float eps, float* out, int mode, void* workspace,
-                    size_t workspace_bytes, const void* wc_planes, void* kv_planes, void* stream_) {
+                    size_t workspace_bytes, const void* wc_planes, void* kv_planes, void* out_planes, void* stream_) {
     if (!x || !y || !w1_planes || !w2_planes || !gamma || !beta || !out || m <= 0 || hidden < 64 || hidden % 32 != 0 ||
         (mode != 0 && mode != 1) || wshift < 0 || wshift > 14) {
         um_set_error("um_ffn_fwd: bad argument (m=%d hidden=%d wshift=%d mode=%d; hidden must be a multiple of 32, >= 64)",
@@ -1062,6 +1097,8 @@ static int ffn_impl(const float* x, const float* y, const void* w1_planes, const
     a.hs_part = nullptr;
     a.hs_flag = nullptr;
     a.kv = Kv4Args{};
+    a.planes = nullptr;
+    a.planes_stride = (long)m * 128;
     a.range_flag = a.kv.range_flag = (mode == 0) ? um_range_flag_dev() : nullptr;
     if (workspace) {
         const int split = ffn_hidden_split(m, hidden);
@@ -1083,12 +1120,20 @@ static int ffn_impl(const float* x, const float* y, const void* w1_planes, const
         a.kv.M = m;
         a.kv.out_scale = a.out_scale;
     }
+    if (out_planes && a.split == 1) a.planes = (unsigned short*)out_planes;
     const hipError_t e = mode == 0 ? launch_ffn<Fp16, 2>(a, (hipStream_t)stream_) : launch_ffn<Bf16, 1>(a, (hipStream_t)stream_);
     if (e != hipSuccess) {
         um_set_error("um_ffn_fwd: launch failed: %s", hipGetErrorString(e));
         return (int)e;
     }
     if (wc_planes && !fuse) return um_kv4_fwd(out, wc_planes, m, wshift, kv_planes, mode, stream_);
+    if (out_planes && !a.planes) {
+        const hipError_t es = launch_split_planes(out, (unsigned short*)out_planes, m, 1.f, mode, (hipStream_t)stream_);
+        if (es != hipSuccess) {
+            um_set_error("um_ffn_planes_fwd: format pass failed: %s", hipGetErrorString(es));
+            return (int)es;
+        }
+    }
     return 0;
 }
 

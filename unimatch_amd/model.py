@@ -112,14 +112,16 @@ class TransformerLayer(nn.Module):
                                      nn.Linear(2 * d_model * ffn_dim_expansion, d_model, bias=False))
             self.norm2 = nn.LayerNorm(d_model)
 
-    def forward(self, ops, source, target, h, w, geom, kv_rotate=0, kv=None, next_kv_weights=None):
+    def forward(self, ops, source, target, h, w, geom, kv_rotate=0, kv=None, next_kv_weights=None, fold=False, next_planes=False):
         """``kv_rotate = r`` (fused path only): ``target`` holds the streams in the SAME order as ``source`` and stream ``s``
         attends the keys / values of stream ``(s + r) mod S`` -- the swapped copy ``[f1; f0]`` is never built.
         ``kv = (k_operand, v_operand)``: the layer's key / value projections of ``target`` already exist as operand planes
-        (``ops.kv4_slices``: the block projects both layers' k | v in one launch, or the previous block's FFN epilogue wrote them)."""
+        (``ops.kv4_slices``: the block projects both layers' k | v in one launch, or the previous block's FFN epilogue wrote them).
+        ``fold``: ``kv`` holds the planes of ``target`` ITSELF, twice, and the attention runs with the folded weights ``Wk^T Wq`` /
+        ``Wm Wv`` (``ops.fold_kv``); ``next_planes``: the FFN launch also returns the planes of its result, the next block's ``kv``."""
         if getattr(ops, 'fused_tail', False):
-            return self._forward_fused(ops, source, target, h, w, geom, kv_rotate, kv, next_kv_weights)
-        assert kv_rotate == 0 and kv is None and next_kv_weights is None
+            return self._forward_fused(ops, source, target, h, w, geom, kv_rotate, kv, next_kv_weights, fold, next_planes)
+        assert kv_rotate == 0 and kv is None and next_kv_weights is None and not fold and not next_planes
         q, k, v = self.q_proj(source), self.k_proj(target), self.v_proj(target)
         msg = ops.window_attention(q, k, v, h, w, *geom)
         msg = self.norm1(self.merge(msg))
@@ -127,7 +129,7 @@ class TransformerLayer(nn.Module):
             msg = self.norm2(self.mlp(torch.cat([source, msg], dim=-1)))
         return source + msg
 
-    def _forward_fused(self, ops, source, target, h, w, geom, kv_rotate=0, kv=None, next_kv_weights=None):
+    def _forward_fused(self, ops, source, target, h, w, geom, kv_rotate=0, kv=None, next_kv_weights=None, fold=False, next_planes=False):
         """Same layer on the fused HIP path: projections emit attention operand planes, merge + LayerNorm
         (+ residual) is one kernel, the FFN is one kernel (``um_ffn_fwd``; or two without ``ops.fused_ffn``).
         ``next_kv_weights``: the four k | v projection weights of the NEXT block -- the FFN launch then also returns that
@@ -137,6 +139,7 @@ class TransformerLayer(nn.Module):
         src = source.reshape(m, c)
         if getattr(ops, 'fused_qproj', False) and getattr(ops, 'fused_merge', False):
             # q is projected inside the attention kernel's prologue (um_window_attn_qproj_merge_fwd): only k | v planes exist
+            assert not fold or (kv is not None and next_kv_weights is None), 'the folded layer reads the planes of the stream itself'
             if kv is None:
                 kvp, _, n2 = ops.linear_planes(target.reshape(m, c), (self.k_proj.weight, self.v_proj.weight))
                 koff, voff = 0, c
@@ -145,11 +148,18 @@ class TransformerLayer(nn.Module):
                 kop, vop = kv                                   # attention operands prepared by the block (ops.kv4_slices)
                 assert kop[1] == m
             res = src if self.no_ffn else None
-            msg = ops.window_attention_qproj_merge(src, self.q_proj.weight, kop, vop, s, h, w, *geom,
-                                                   kv_rotate, self.merge.weight, self.norm1, res)
+            if fold:                                            # keys = values = the tokens: k_proj / v_proj live in the folded weights
+                msg = ops.window_attention_qproj_merge(src, self.q_proj.weight, kop, vop, s, h, w, *geom, kv_rotate, self.merge.weight,
+                                                       self.norm1, res, fold=(self.k_proj.weight, self.v_proj.weight))
+            else:
+                msg = ops.window_attention_qproj_merge(src, self.q_proj.weight, kop, vop, s, h, w, *geom,
+                                                       kv_rotate, self.merge.weight, self.norm1, res)
             if self.no_ffn:
                 return msg
             msg = msg.reshape(m, c)
+            if next_planes:
+                out, npl = ops.ffn_ln(src, msg, self.mlp[0].weight, self.mlp[2].weight, self.norm2, planes=True)
+                return out.reshape(s, l, c), npl
             if next_kv_weights is not None:
                 out, nkv = ops.ffn_ln_kv(src, msg, self.mlp[0].weight, self.mlp[2].weight, self.norm2, next_kv_weights)
                 return out.reshape(s, l, c), nkv
@@ -157,7 +167,8 @@ class TransformerLayer(nn.Module):
                 return ops.ffn_ln(src, msg, self.mlp[0].weight, self.mlp[2].weight, self.norm2).reshape(s, l, c)
             hid, _, nh = ops.linear_planes(src, (self.mlp[0].weight,), a1=msg, gelu=True)
             return ops.linear_ln(hid, (self.mlp[2].weight,), self.norm2, residual=src, a_planes_k=nh).reshape(s, l, c)
-        assert kv is None and next_kv_weights is None, 'precomputed k | v planes need the fused q-projection / merge path'
+        assert kv is None and next_kv_weights is None and not fold and not next_planes, \
+            'precomputed k | v planes need the fused q-projection / merge path'
         if target is source:                       # self attention: one projection launch for q | k | v
             qkv, _, n3 = ops.linear_planes(src, (self.q_proj.weight, self.k_proj.weight, self.v_proj.weight))
             q, k, v = (qkv, m, n3, 0), (qkv, m, n3, c), (qkv, m, n3, 2 * c)
@@ -211,12 +222,21 @@ class FeatureTransformer(nn.Module):
         b = stream.shape[0] // 2
         rotate = getattr(ops, 'fused_tail', False)     # cross-attention target [f1; f0] = `prev` read with the halves rotated
         prev = stream if rotate else torch.cat([stream[b:], stream[:b]], 0)
-        # both layers of a block read their keys / values from the stream AS IT ENTERS the block (self: the stream itself; cross:
-        # its halves rotated), so the four projections Wk_self | Wv_self | Wk_cross | Wv_cross are ONE launch that reads the
-        # stream once and writes blocked operand planes [NS][4][M][128] (um_kv4_fwd; round 4 -- was two um_linear_fwd launches of
-        # two projections each: transformer.py:58-60 per layer)
-        block_kv = rotate and getattr(ops, 'fused_qproj', False) and getattr(ops, 'fused_merge', False) and getattr(ops, 'block_kv', True)
+        fused_attn = rotate and getattr(ops, 'fused_qproj', False) and getattr(ops, 'fused_merge', False)
         s2, l, c = stream.shape
+        # both layers of a block read their keys / values from the stream AS IT ENTERS the block (self: the stream itself; cross:
+        # its halves rotated).  ops.fold_kv: no k | v projection at all.  The layer is single-head and bias-free with nothing
+        # non-linear between the projections and the attention (transformer.py:23-27, 58-60, 137), so k_proj / v_proj are folded into
+        # the query and merge weights (ops.fold_weights) and keys = values = the stream: ONE planes tensor [NS][M][128] of the entering
+        # stream serves both layers of the block -- block 0's by one format pass, every later one's written by the previous block's
+        # FFN launch (um_ffn_planes_fwd).  block_kv / fused_kv then play no role.
+        fold = fused_attn and getattr(ops, 'fold_kv', False)
+        fold_ffn = fold and getattr(ops, 'fused_ffn', False)
+        planes = None
+        # without the fold the four projections Wk_self | Wv_self | Wk_cross | Wv_cross are ONE launch that reads the stream once and
+        # writes blocked operand planes [NS][4][M][128] (um_kv4_fwd; round 4 -- was two um_linear_fwd launches of two projections
+        # each: transformer.py:58-60 per layer)
+        block_kv = fused_attn and not fold and getattr(ops, 'block_kv', True)
         # ... and from block 1 on they come out of the previous block's FFN launch (um_ffn_kv_fwd): no projection launch at all
         fused_kv = block_kv and getattr(ops, 'fused_kv', False) and getattr(ops, 'fused_ffn', False)
         kv4 = None
@@ -227,17 +247,26 @@ class FeatureTransformer(nn.Module):
             g_self = attention_windows(attn_type, True, attn_num_splits, h, w, shift)
             g_cross = attention_windows(attn_type, False, attn_num_splits, h, w, shift)
             kv_s = kv_c = None
+            if fold:
+                if planes is None:                     # block 0 (or the two-launch FFN): the stand-alone format pass
+                    planes, _, _ = ops.linear_planes(stream.reshape(s2 * l, c), ())
+                kv_s = kv_c = ((planes, s2 * l, c, 0),) * 2
+                planes = None
             if block_kv:
                 if kv4 is None:                        # block 0 (or fused_kv off): the stand-alone launch
                     kv4 = ops.kv4_planes(stream.reshape(s2 * l, c), kvw(blk))
                 kv_s, kv_c = ops.kv4_slices(kv4, s2 * l)
                 kv4 = None
-            stream = blk.self_attn(ops, stream, stream, h, w, g_self, kv=kv_s)
+            stream = blk.self_attn(ops, stream, stream, h, w, g_self, kv=kv_s, fold=fold)
             if rotate:                                 # keys / values come from the stream as it was before this block
                 nxt = kvw(self.layers[i + 1]) if fused_kv and i + 1 < len(self.layers) else None
-                stream = blk.cross_attn_ffn(ops, stream, prev, h, w, g_cross, kv_rotate=b, kv=kv_c, next_kv_weights=nxt)
+                nxp = fold_ffn and i + 1 < len(self.layers)
+                stream = blk.cross_attn_ffn(ops, stream, prev, h, w, g_cross, kv_rotate=b, kv=kv_c, next_kv_weights=nxt, fold=fold,
+                                            next_planes=nxp)
                 if nxt is not None:
                     stream, kv4 = stream
+                elif nxp:
+                    stream, planes = stream
                 prev = stream
             else:
                 stream = blk.cross_attn_ffn(ops, stream, prev, h, w, g_cross)

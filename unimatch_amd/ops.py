@@ -68,6 +68,19 @@ def pack_kv4_weights(weights):
     return torch.cat([w4[:256], cross], 1).contiguous()
 
 
+def fold_weights(kind, a, b):
+    """The folded ``[128, 128]`` weight of one attention layer, formed in fp64 and rounded once to fp32.  The layer is single-head, its
+    Linears are bias-free and nothing non-linear sits between the projections and the attention (transformer.py:23-27, 58-60, 137), so
+    ``(x Wq^T)(y Wk^T)^T = (x (Wk^T Wq)^T) y^T`` and ``merge(P (y Wv^T)) = (P y)(Wm Wv)^T``:
+    ``kind='q'``: ``a, b = Wk, Wq -> Wk^T Wq``;  ``kind='m'``: ``a, b = Wm, Wv -> Wm Wv``.  Sum over the middle index without a BLAS call."""
+    a, b = a.detach().double(), b.detach().double()
+    if kind == 'q':
+        a = a.t()
+    elif kind != 'm':
+        raise ValueError(f"fold_weights: kind must be 'q' or 'm', got {kind!r}")
+    return (a.unsqueeze(2) * b.unsqueeze(0)).sum(1).float().contiguous()
+
+
 WorkspaceKey = namedtuple('WorkspaceKey', 'kind geometry device owner')
 
 
@@ -150,7 +163,12 @@ class HipOps(WorkspaceRegistry):
     fused_qproj = True         # ... and the query projection in its prologue (um_window_attn_qproj_merge_fwd)
     block_kv = True            # one k | v projection launch per Transformer block (both layers' keys / values: um_kv4_fwd)
     refine_hoist = True        # refinement loop: the iteration-invariant share of the GRU gate convolutions computed once per scale
-    fused_kv = True            # ... which, from block 1 on, is the previous block's FFN epilogue (um_ffn_kv_fwd): no launch at all
+    fused_kv = False           # ... which, from block 1 on, is the previous block's FFN epilogue (um_ffn_kv_fwd): no launch at all.
+                               #     block_kv / fused_kv only act with fold_kv off; fold_kv = 0 with fused_kv = 1 is the forward before the fold
+                               #     (off by default because bench.py prices the FFN launches' k | v FLOPs by this attribute)
+    fold_kv = True             # k_proj / v_proj folded into the query and merge weights (q' = Wk^T Wq, merge' = Wm Wv, fold_weights): keys =
+                               #     values = the token stream itself, one [NS][M][128] planes tensor per block, written by the previous
+                               #     block's FFN launch (um_ffn_planes_fwd) or, for block 0, by one format pass
     # (class attributes: tests and tools/ab_bench.py flip them programmatically; the product reads no environment variable)
     fused_conv = True          # encoder convolutions + InstanceNorm in NHWC on um_conv2d_fwd / um_nhwc_instance_norm
     norm_on_load = True        # ... a residual block's middle InstanceNorm + ReLU inside its second convolution (um_conv2d_norm_fwd)
@@ -254,6 +272,16 @@ class HipOps(WorkspaceRegistry):
                    'um_weight_planes')
         return self._cache_put(key, weights, (planes, n, k))
 
+    def _folded_weight(self, kind, a, b):
+        """:func:`fold_weights` of the two parameters, cached like their planes (identity + version; ``invalidate_weights``).  The planes
+        of the result come from :meth:`weight_planes`, keyed by this tensor: they live exactly as long as this entry."""
+        key, hit = self._cache_get('fold_' + kind, (a, b))
+        if hit is not None:
+            return hit
+        if tuple(a.shape) != (128, 128) or tuple(b.shape) != (128, 128):
+            raise ValueError('folded attention weights: expected two [128, 128] weights')
+        return self._cache_put(key, (a, b), fold_weights(kind, a, b))
+
     @staticmethod
     def _check_weight_range(w, shift, what):
         """Exact mode stores weights as fp16 hi + lo planes of ``w * 2^shift``: anything at or above 65504 / 2^shift would become
@@ -272,7 +300,17 @@ class HipOps(WorkspaceRegistry):
         """``(gelu)(A . cat(weights)^T)`` written as MFMA operand planes ``[NS][M][N]`` (flat uint8 tensor).
 
         A is ``a`` fp32 ``[M, K]``, or the K-concatenation of ``a`` and ``a1`` (``[M, K/2]`` each), or -- with
-        ``a_planes_k`` -- ``a`` is already a plane tensor with K = a_planes_k columns."""
+        ``a_planes_k`` -- ``a`` is already a plane tensor with K = a_planes_k columns.  ``weights = ()``: the identity -- the planes
+        of ``a`` itself, one format pass (``um_weight_planes`` at scale 1): the key / value operand of the folded attention."""
+        if len(weights) == 0:
+            if a1 is not None or gelu or a_planes_k is not None or not (a.dim() == 2 and a.shape[0] > 0):
+                raise ValueError('linear_planes: the identity takes one fp32 [M, K] tensor and no epilogue')
+            m, k = a.shape
+            self._check_rows('a', a, k)
+            out = torch.empty(self.lib.um_planes_bytes(m, k, self.mode), dtype=torch.uint8, device=a.device)
+            _abi.check(self._launch('split_planes', lambda: self.lib.um_weight_planes(_ptr(a), _ptr(out), m, k, 0, self.mode, _stream())),
+                       'um_weight_planes')
+            return out, m, k
         wp, n, k = self.weight_planes(weights)
         if a_planes_k is not None:
             m = a.numel() // (2 * self.nplanes * a_planes_k)
@@ -311,9 +349,11 @@ class HipOps(WorkspaceRegistry):
         _abi.check(code, 'um_linear_fwd')
         return out
 
-    def ffn_ln(self, x, y, w1, w2, norm):
+    def ffn_ln(self, x, y, w1, w2, norm, planes=False):
         """``x + LayerNorm(W2 . gelu(W1 . [x | y]))`` in one kernel (``um_ffn_fwd``); x, y fp32 ``[M, 128]``,
-        ``w1`` ``[hidden, 256]``, ``w2`` ``[128, hidden]``, ``norm`` an ``nn.LayerNorm`` over 128."""
+        ``w1`` ``[hidden, 256]``, ``w2`` ``[128, hidden]``, ``norm`` an ``nn.LayerNorm`` over 128.  ``planes``: the same launch also
+        writes the result's operand planes ``[NS][M][128]`` (``um_ffn_planes_fwd``; bit for bit ``linear_planes(out, ())``) -> ``(out,
+        planes)``: the next block's keys / values when the k | v projections are folded away."""
         w1p, hid, k1 = self.weight_planes((w1,))
         w2p, n2, k2 = self.weight_planes((w2,))
         if (k1, n2, k2) != (256, 128, hid):
@@ -325,6 +365,14 @@ class HipOps(WorkspaceRegistry):
             raise ValueError('ffn_ln: x and y must have the same number of rows')
         out = torch.empty((m, 128), dtype=torch.float32, device=x.device)
         ws = self._split_workspace('ffn_hsplit', (m, hid), x.device)
+        if planes:
+            pl = torch.empty(self.lib.um_planes_bytes(m, 128, self.mode), dtype=torch.uint8, device=x.device)
+            code = self._launch('ffn', lambda: self.lib.um_ffn_planes_fwd(
+                _ptr(x), _ptr(y), _ptr(w1p), _ptr(w2p), m, hid, self.WSHIFT, _ptr(norm.weight), _ptr(norm.bias),
+                float(norm.eps), _ptr(out), _ptr(pl), self.mode, _ptr(ws) if ws is not None else None,
+                ws.numel() if ws is not None else 0, _stream()), {'flops': 2.0 * m * hid * (256 + 128)})
+            _abi.check(code, 'um_ffn_planes_fwd')
+            return out, pl
         code = self._launch('ffn', lambda: self.lib.um_ffn_ws_fwd(
             _ptr(x), _ptr(y), _ptr(w1p), _ptr(w2p), m, hid, self.WSHIFT, _ptr(norm.weight), _ptr(norm.bias),
             float(norm.eps), _ptr(out), self.mode, _ptr(ws) if ws is not None else None, ws.numel() if ws is not None else 0,
@@ -400,9 +448,11 @@ class HipOps(WorkspaceRegistry):
         return self._workspace(kind, geometry, nbytes, device, self.GEOMETRIES) if nbytes else None
 
     def window_attention_qproj_merge(self, x, q_weight, k, v, streams, h, w, win_h, win_w, shift_h, shift_w, kv_rotate,
-                                     merge_weight, norm, residual=None):
+                                     merge_weight, norm, residual=None, fold=None):
         """:meth:`window_attention_merge` with ``q = x . Wq^T`` computed in the kernel's prologue
-        (``um_window_attn_qproj_merge_fwd``): ``x`` fp32 ``[streams*h*w, 128]`` source tokens, ``q_weight`` ``[128, 128]``."""
+        (``um_window_attn_qproj_merge_fwd``): ``x`` fp32 ``[streams*h*w, 128]`` source tokens, ``q_weight`` ``[128, 128]``.
+        ``fold = (k_weight, v_weight)``: ``k`` and ``v`` are the planes of the UNPROJECTED key / value tokens and the kernel runs with
+        the folded weights ``Wk^T Wq`` and ``Wm Wv`` (:func:`fold_weights`) -- the same logits and messages with no k | v projection."""
         # k, v: (plane tensor, rows, row stride in elements, element offset of the first row[, plane stride in elements]) -- the
         # optional fifth entry describes slices of a bigger plane tensor (the blocked [NS][4][M][128] k | v planes of kv4_planes)
         (kt, krows, kcols, koff), (vt, vrows, vcols, voff) = k[:4], v[:4]
@@ -412,6 +462,8 @@ class HipOps(WorkspaceRegistry):
         self._check_rows('x', x, 128)
         if (krows, kcols) != (vrows, vcols) or x.shape[0] != streams * h * w or krows != x.shape[0]:
             raise ValueError('inconsistent plane shapes')
+        if fold is not None:
+            q_weight, merge_weight = self._folded_weight('q', fold[0], q_weight), self._folded_weight('m', merge_weight, fold[1])
         wqp, nq, kq = self.weight_planes((q_weight,))
         wp, n, kk = self.weight_planes((merge_weight,))
         if (n, kk, nq, kq) != (128, 128, 128, 128):
