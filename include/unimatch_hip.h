@@ -41,7 +41,8 @@
 extern "C" {
 #endif
 
-#define UM_VERSION 220   /* 220 also gained um_global_match_stats_workspace_bytes, um_global_match_stats and um_match_mutual */
+#define UM_VERSION 220   /* 220 also gained um_global_match_stats_workspace_bytes, um_global_match_stats and um_match_mutual,
+                            um_depth_corr_softmax_multi */
 
 #define UM_MODE_EXACT 0
 #define UM_MODE_FAST 1
@@ -585,6 +586,26 @@ int um_depth_corr_softmax(const float* f0, const float* f1, const float* cam, co
 int um_depth_corr_softmax_stats(const float* f0, const float* f1, const float* cam, const float* candidates,
                                 float* out, float* stats, int* index,
                                 int batch, int h, int w, int channels, int num_candidates,
+                                int from_argmax, int peak_radius, void* stream);
+
+/* The plane sweep with several source views voting in ONE cost volume before the softmax (csrc/depth_multi.hip).  Sources
+ * s = 0 .. S-1 share the reference pixel and the candidates c_j.  For a source that is on, l_sj is exactly the logit
+ * um_depth_corr_softmax forms for (f0_s, f1_s, cam_s) and v_sj = 1 when candidate j has a bilinear corner inside the image of
+ * source s (x0 in [-1, w-1] and y0 in [-1, h-1]).  Fused:
+ *   n_j = sum_s v_sj,   l_j = (sum_s v_sj l_sj) / max(1, n_j),   p = softmax_j l_j
+ * -- a mean over the sources that SEE the candidate, which keeps the logits at the scale the softmax was trained at.  This is an
+ * UNLEARNED extension: the weights are trained on two views.  out, stats and index are those of um_depth_corr_softmax_stats taken
+ * on p (best = first arg-max of l, in_view = candidates with n_j >= 1).  One source given 2 or 4 times gives bit for bit the S = 1
+ * result (2l/2 and 4l/4 are exact), and S = 1 gives bit for bit the result of um_depth_corr_softmax_stats.
+ *   f0, f1 [S, B, h*w, 128] (each source has its own f0_s: after cross-attention the reference tokens depend on the partner view),
+ *   cam [S, B, 30], use [S, B] bytes (0: the source is off for that sample and is never read) or NULL = all on,
+ *   out [B, 1, h, w], stats [B, 4, h, w] or NULL, index [B, 2, h, w] or NULL.  Source-major: S = 1 is the two-view layout.
+ * `use` lives on the device and is not inspected by the host: a sample whose sources are all off gets the uniform distribution
+ * (every logit 0, in_view 0).  Errors (negative, nothing launched): a null f0 / f1 / cam / candidates / out, channels != 128,
+ * num_candidates outside 1 .. 128, sources outside 1 .. 8, peak_radius < 0. */
+int um_depth_corr_softmax_multi(const float* f0, const float* f1, const float* cam, const unsigned char* use,
+                                const float* candidates, float* out, float* stats, int* index,
+                                int sources, int batch, int h, int w, int channels, int num_candidates,
                                 int from_argmax, int peak_radius, void* stream);
 
 /* ---------------------------------------------------------------------------------------------

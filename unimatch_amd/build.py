@@ -14,10 +14,10 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libunimatch_hip.so')
 SOURCES = ['capi.hip', 'global_match.hip', 'window_attn.hip', 'local_ops.hip', 'linear.hip', 'ffn.hip', 'conv.hip', 'nhwc_ops.hip', 'norm_ops.hip', 'upsample.hip',
            'rccl_gather.hip', 'local_corr_mfma.hip', 'aliases.hip', 'probe.hip', 'video.hip', 'metrics.hip', 'prepost.hip', 'visualize.hip', 'geometry.hip', 'match_stats.hip',
-           'interp.hip']
+           'interp.hip', 'depth_multi.hip']
 # hardware micro-benchmarks (um_debug_*): diagnostic builds only, never in the shipped library
 DIAG_SOURCES = ['microbench.hip']
-HEADERS = ['common.h', 'planes.h', 'timing.h', os.path.join('..', '..', 'include', 'unimatch_hip.h')]
+HEADERS = ['common.h', 'planes.h', 'timing.h', 'local_pixel.h', os.path.join('..', '..', 'include', 'unimatch_hip.h')]
 # per-file extras: the FFN kernel's hand-placed scalar VALU stream must not be re-packed into v_pk_* by the SLP vectorizer
 EXTRA_FLAGS = {'ffn.hip': ['-fno-slp-vectorize'], 'global_match.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form', '-Wno-inline-asm'], 'window_attn.hip': ['-fno-slp-vectorize'],
                'linear.hip': ['-fno-slp-vectorize'],
@@ -42,6 +42,8 @@ RESOURCE_GUARDS = {'conv.hip': {'conv_entry_kernel': 2},
                    # the plane sweep (K7), plain and with statistics: no scratch in any of the four kernels, three waves per SIMD as before the statistics
                    'local_ops.hip': {'depth_corr_softmax_kernel': 3, 'depth_corr_softmax_box_kernel': 3, 'depth_corr_softmax_stats_kernel': 3,
                                      'depth_corr_softmax_box_stats_kernel': 3},
+                   # the multi-view plane sweep: the same table and the same three waves as K7's box form, no scratch
+                   'depth_multi.hip': {'depth_multi_box_kernel': 3, 'depth_multi_gather_kernel': 3},
                    # memory-bound per-pixel kernels: no scratch, and registers far below what would cost a wave
                    'geometry.hip': {'disp_consistency_kernel': 4, 'depth_consistency_kernel': 4, 'points_count_kernel': 4,
                                     'points_scan_kernel': 4, 'points_scatter_kernel': 4},

@@ -32,6 +32,10 @@ Depth has its own distribution: the plane sweep's ``match_prob [B, D, h, w]`` ov
 
 CUDA tensors run ``um_depth_corr_softmax_stats`` (csrc/local_ops.hip: the sweep's own launch also writes the statistics); host tensors
 run ``depth_match_prob_host`` / ``depth_stats_from_prob_host``, the reference's ``match_prob`` from the packed camera record.
+
+  depth_match_multi(f0, f1, h, w, cam, candidates, use=)          several source views ``[S, B, ...]`` vote in one sweep: the logits are
+                                                                  averaged over the sources that see a candidate, then one softmax
+                                                                  (``um_depth_corr_softmax_multi``; unlearned, the weights know two views)
 """
 from collections import namedtuple
 
@@ -207,6 +211,14 @@ def depth_sample_coords_host(h, w, cam, candidates):
 def depth_match_logits_host(f0, f1, h, w, cam, candidates):
     """``(logits [B, D, h, w], in_view [B, h, w] int32)`` of the plane sweep: feature1 sampled bilinearly with zero padding where each
     candidate lands, correlated with feature0, over ``sqrt(C)``.  ``in_view`` counts the candidates with a corner inside the image."""
+    logits, visible = depth_match_logits_visible_host(f0, f1, h, w, cam, candidates)
+    return logits, visible.sum(1).to(torch.int32)
+
+
+def depth_match_logits_visible_host(f0, f1, h, w, cam, candidates):
+    """:func:`depth_match_logits_host` with the per-candidate visibility instead of its count: ``(logits [B, D, h, w], visible
+    [B, D, h, w] bool)``, ``visible`` = the candidate has a bilinear corner inside the image (``x0`` in ``[-1, w-1]``, ``y0`` in
+    ``[-1, h-1]``)."""
     _check_depth_inputs(f0, f1, h, w, cam, candidates)
     b, l, c = f0.shape
     dt = f0.dtype
@@ -225,8 +237,8 @@ def depth_match_logits_host(f0, f1, h, w, cam, candidates):
             wt = ((wx if cx else 1 - wx) * (wy if cy else 1 - wy)).view(b, d, l)
             rows = f1[batch, (yy.clamp(0, h - 1) * w + xx.clamp(0, w - 1))]            # [B, D, L, C]
             corr = corr + torch.where(ok, wt * (a * rows).sum(-1), torch.zeros((), dtype=dt, device=f0.device))
-    seen = ((x0 >= -1) & (x0 < w) & (y0 >= -1) & (y0 < h)).sum(1).to(torch.int32)
-    return (corr / c ** 0.5).view(b, d, h, w), seen
+    visible = (x0 >= -1) & (x0 < w) & (y0 >= -1) & (y0 < h)
+    return (corr / c ** 0.5).view(b, d, h, w), visible
 
 
 def depth_match_prob_host(f0, f1, h, w, cam, candidates):
@@ -306,6 +318,81 @@ def depth_match_confidence(ops, f0, f1, h, w, cam, candidates, from_argmax, scal
         s = depth_match_stats_host(f0, f1, h, w, cam, candidates, int(peak_radius))
     conf = dict(s._asdict(), scale=int(scale), num_candidates=int(candidates.numel()))
     return out, conf
+
+
+# ------------------------------------------------------------------ depth: several source views in one plane sweep
+def _check_multi_inputs(f0, f1, h, w, cam, candidates, use):
+    if f0.dim() != 4 or not 1 <= f0.shape[0] <= 8:
+        raise ValueError(f'expected source-major features [S = 1 .. 8, B, h*w, C], got {tuple(f0.shape)}')
+    if cam.dim() != 3 or cam.shape[0] != f0.shape[0]:
+        raise ValueError(f'cam: expected [{f0.shape[0]}, {f0.shape[1]}, 30], got {tuple(cam.shape)}')
+    if f1.shape != f0.shape:
+        raise ValueError(f'f1: expected {tuple(f0.shape)}, got {tuple(f1.shape)}')
+    for s in range(f0.shape[0]):
+        _check_depth_inputs(f0[s], f1[s], h, w, cam[s], candidates)
+    if use is not None and (tuple(use.shape) != tuple(f0.shape[:2]) or use.device != f0.device):
+        raise ValueError(f'use: expected [{f0.shape[0]}, {f0.shape[1]}] on {f0.device}, got {tuple(use.shape)} on {use.device}')
+
+
+def depth_match_logits_multi_host(f0, f1, h, w, cam, candidates, use=None):
+    """The fused logits of the multi-view plane sweep (``um_depth_corr_softmax_multi``), in the dtype of the inputs.  ``f0``, ``f1``
+    ``[S, B, h*w, C]``, ``cam [S, B, 30]``, ``use [S, B]`` (false: the source is off for that sample and is not read) or None.  With
+    ``l_sj`` the logit and ``v_sj`` the visibility of :func:`depth_match_logits_visible_host` for source ``s``:
+
+        ``n_j = sum_s v_sj``,   ``l_j = (sum_s v_sj l_sj) / max(1, n_j)``
+
+    -- a mean over the sources that see the candidate (an unlearned extension: the weights are trained on two views).  Returns
+    ``(logits [B, D, h, w], in_view [B, h, w] int32 = candidates with n_j >= 1, views [B, D, h, w] int32 = n_j)``."""
+    _check_multi_inputs(f0, f1, h, w, cam, candidates, use)
+    s_count, b = f0.shape[:2]
+    d = candidates.numel()
+    total = torch.zeros((b, d, h, w), dtype=f0.dtype, device=f0.device)
+    views = torch.zeros((b, d, h, w), dtype=torch.int32, device=f0.device)
+    on = torch.ones((s_count, b), dtype=torch.bool) if use is None else use.to(torch.bool).cpu()
+    for s in range(s_count):
+        rows = torch.nonzero(on[s]).flatten().to(f0.device)
+        if rows.numel() == 0:
+            continue
+        logits, visible = depth_match_logits_visible_host(f0[s][rows], f1[s][rows], h, w, cam[s][rows], candidates)
+        total[rows] = total[rows] + torch.where(visible, logits, torch.zeros((), dtype=f0.dtype, device=f0.device))
+        views[rows] = views[rows] + visible.to(torch.int32)
+    fused = total / views.clamp(min=1).to(f0.dtype)
+    return fused, (views >= 1).sum(1).to(torch.int32), views
+
+
+def depth_match_stats_multi_host(f0, f1, h, w, cam, candidates, use=None, peak_radius=1):
+    """``DepthMatchStats`` of the fused distribution ``softmax_j l_j`` of :func:`depth_match_logits_multi_host`, which it forms."""
+    logits, seen, _ = depth_match_logits_multi_host(f0, f1, h, w, cam, candidates, use)
+    return depth_stats_from_prob_host(torch.softmax(logits, 1), candidates, seen, peak_radius)
+
+
+def depth_match_multi(f0, f1, h, w, cam, candidates, use=None, *, from_argmax=False, peak_radius=1, ops=None):
+    """The multi-view plane sweep: ``(out [B, 1, h, w], DepthMatchStats)`` of the source-major ``f0``, ``f1`` ``[S, B, h*w, 128]`` under
+    ``cam [S, B, 30]`` over the inverse-depth ``candidates [D]``; ``use [S, B]`` switches sources off per sample.  ``out`` is the
+    soft-argmin of the fused distribution (``from_argmax``: the candidate at ``best``).  CUDA tensors run ONE
+    ``um_depth_corr_softmax_multi`` launch (through ``ops``, a ``HipOps``, when given: its launch record sees the call); host tensors
+    run the restatement above.  There is no fallback from one to the other.  The fusion is unlearned: see csrc/depth_multi.hip."""
+    _check_multi_inputs(f0, f1, h, w, cam, candidates, use)
+    if int(peak_radius) < 0:
+        raise ValueError(f'peak_radius must be >= 0, got {peak_radius}')
+    if not f0.is_cuda:
+        logits, seen, _ = depth_match_logits_multi_host(f0, f1, h, w, cam, candidates, use)
+        prob = torch.softmax(logits, 1)
+        st = depth_stats_from_prob_host(prob, candidates, seen, int(peak_radius))
+        cand = candidates.to(prob.dtype)
+        out = cand[st.best.long()][:, None] if from_argmax else (prob * cand.view(1, -1, 1, 1)).sum(1, keepdim=True)
+        return out, st
+    if ops is None:
+        from .ops import HipOps              # raises when the HIP extension is missing: there is no silent fallback
+        ops = HipOps('exact')
+    out, stats, index = ops.depth_corr_softmax(f0, f1, h, w, cam, candidates, from_argmax, stats=True, peak_radius=int(peak_radius), use=use)
+    return out, DepthMatchStats(stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3], index[:, 0], index[:, 1])
+
+
+def depth_match_multi_confidence(ops, f0, f1, h, w, cam, candidates, use, from_argmax, scale, peak_radius=1):
+    """The fused sweep's prediction and its ``'depth_confidence'`` dict (the keys of :func:`depth_match_confidence`)."""
+    out, s = depth_match_multi(f0, f1, h, w, cam, candidates, use, from_argmax=from_argmax, peak_radius=peak_radius, ops=ops)
+    return out, dict(s._asdict(), scale=int(scale), num_candidates=int(candidates.numel()))
 
 
 def confidence_to_image_size(conf_map, scale, geom=None):

@@ -18,50 +18,7 @@
 // four more shuffles.  Token-major feature layout [B, L, 128] fp32.
 #include "common.h"
 #include "timing.h"
-
-#define LOCAL_MAX_ROUNDS 8      // up to 128 taps / depth candidates
-
-// A 128-channel fp32 row (512 B) is shared by the 4 lanes of a tap slot.  Lane quarter q owns channels 16 i + 4 q .. + 3
-// (i = 0..7): callers pass `row + 4 * quarter`, and load i of the four lanes covers 64 CONTIGUOUS bytes -- one request to
-// the L1 per slot and load.  (Round 1 gave each lane 32 consecutive channels: four 16-byte pieces 128 B apart per slot and
-// load, i.e. 64 cache lines touched by every wave instruction; these gather kernels were bound by exactly that.)
-__device__ __forceinline__ void load32(f32x4 (&r)[8], const float* p) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r[i] = reinterpret_cast<const f32x4*>(p)[4 * i];
-}
-
-__device__ __forceinline__ float dot32(const f32x4 (&a)[8], const float* p) {
-    float acc = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const f32x4 b = reinterpret_cast<const f32x4*>(p)[4 * i];
-        acc = __builtin_fmaf(a[i][0], b[0], acc);
-        acc = __builtin_fmaf(a[i][1], b[1], acc);
-        acc = __builtin_fmaf(a[i][2], b[2], acc);
-        acc = __builtin_fmaf(a[i][3], b[3], acc);
-    }
-    return acc;
-}
-
-__device__ __forceinline__ float quad_sum(float v) {      // sum over the 4 channel quarters (lanes 4k..4k+3)
-    v += __shfl_xor(v, 1);
-    v += __shfl_xor(v, 2);
-    return v;
-}
-__device__ __forceinline__ float slot_max(float v) {      // reduce over the 16 tap slots (lane bits 2..5)
-    v = fmaxf(v, __shfl_xor(v, 4));
-    v = fmaxf(v, __shfl_xor(v, 8));
-    v = fmaxf(v, __shfl_xor(v, 16));
-    v = fmaxf(v, __shfl_xor(v, 32));
-    return v;
-}
-__device__ __forceinline__ float slot_sum(float v) {
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 8);
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    return v;
-}
+#include "local_pixel.h"        // load32 / dot32, the slot reductions, DepthPixelStats, DEPTH_BOX: shared with depth_multi.hip
 
 // ------------------------------------------------------------------------------------------------------
 // K3: local correlation + softmax + expected offset
@@ -400,38 +357,6 @@ __global__ __launch_bounds__(256) void prop_local_attn_kernel(const float* __res
 // accumulations (about the mean; over the window around the first arg-max) reduced over the slots like sum e.  peak_mass sums the
 // same e in the same order as sum e: radius 0 gives max_prob and a radius >= D gives 1, bit for bit.  The plain instantiation
 // (STATS = false) is the kernel as it was: same arithmetic, same order, same register count.
-struct DepthPixelStats {
-    float max_prob, entropy, variance, peak_mass;
-    int best, in_view;
-};
-
-// ln of the softmax denominator (1 <= v <= 128), once per pixel.  v = m 2^k with m in [0.75, 1.5): k ln 2 carries the size and is
-// formed in two pieces (k * hi is exact: hi has 16 significant bits), logf(m) is small, so its error is a fraction of an ulp of the
-// result.  A uniform distribution (sum e = D exactly, every other term of the entropy 0) then gives ln D to within one ulp; logf(v)
-// alone is 1.06 ulp off at D = 17, and a log through fp64 costs the box kernel a wave of occupancy (173 VGPRs).
-__device__ __forceinline__ float depth_ln(float v) {
-    int k;
-    float m = frexpf(v, &k);                                   // m in [0.5, 1)
-    if (m < 0.75f) { m *= 2.f; k -= 1; }
-    const float kf = (float)k;
-    return __builtin_fmaf(kf, 0.693145751953125f, __builtin_fmaf(kf, 1.428606765330187e-06f, logf(m)));
-}
-
-__device__ __forceinline__ int slot_sum_i(int v) {
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 8);
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    return v;
-}
-__device__ __forceinline__ int slot_min_i(int v) {
-    v = min(v, __shfl_xor(v, 4));
-    v = min(v, __shfl_xor(v, 8));
-    v = min(v, __shfl_xor(v, 16));
-    v = min(v, __shfl_xor(v, 32));
-    return v;
-}
-
 template <bool STATS>
 __device__ __forceinline__ float depth_pixel_gather(const float* __restrict__ f0, const float* __restrict__ f1, const float* cm,
                                                     const float* __restrict__ cand, long pid, int b, int h, int w, int nd,
@@ -541,23 +466,6 @@ __device__ __forceinline__ float depth_pixel_gather(const float* __restrict__ f0
     return res;
 }
 
-// lane 0 of the pixel's wave writes the statistics planes (stats [B, 4, h, w], index [B, 2, h, w]; either may be null)
-__device__ __forceinline__ void depth_stats_store(float* __restrict__ stats, int* __restrict__ index, int b, int p, int L,
-                                                  const DepthPixelStats& st) {
-    if (stats) {
-        float* sp = stats + (long)b * 4 * L + p;
-        sp[0] = st.max_prob;
-        sp[L] = st.entropy;
-        sp[2 * (long)L] = st.variance;
-        sp[3 * (long)L] = st.peak_mass;
-    }
-    if (index) {
-        int* ip = index + (long)b * 2 * L + p;
-        ip[0] = st.best;
-        ip[L] = st.in_view;
-    }
-}
-
 template <bool STATS>
 __device__ __forceinline__ void depth_corr_softmax_body(const float* __restrict__ f0, const float* __restrict__ f1,
                                                         const float* __restrict__ cam, const float* __restrict__ cand,
@@ -616,7 +524,6 @@ __global__ __launch_bounds__(256) void depth_corr_softmax_stats_kernel(const flo
 // the dots is the dot with the blended row; summation order differs from the gather form by fp32 rounding only).  A box of more
 // than DEPTH_BOX rows (a camera move with a long diagonal epipolar segment) takes the gather path for that pixel.
 // STATS: lane = candidate, so the statistics (see depth_pixel_gather) are wave reductions of per-lane values.
-#define DEPTH_BOX 160
 template <bool STATS>
 __device__ __forceinline__ void depth_corr_softmax_box_body(const float* __restrict__ f0, const float* __restrict__ f1,
                                                             const float* __restrict__ cam, const float* __restrict__ cand,
@@ -757,13 +664,6 @@ static int local_check(const void* a, const void* b, const void* c, int batch, i
         return -1;
     }
     return 0;
-}
-
-static unsigned pixel_grid_blocks(long pixels) {
-    long blocks = (pixels + 3) / 4;
-    const long cap = 256 * 16;           // 16 workgroups per CU, grid-stride beyond
-    if (blocks > cap) blocks = cap;
-    return (unsigned)(blocks < 1 ? 1 : blocks);
 }
 
 extern "C" int um_local_corr_softmax(const float* f0, const float* f1, float* out, int batch, int h, int w,

@@ -32,7 +32,7 @@ from .refine import BasicUpdateBlock, convex_upsample
 from .refine_nhwc import NhwcUpdateBlock
 from .dist import shard_batch, shard_bounds
 from .streams import PartRunner, forward_parts
-from .confidence import depth_match_confidence, match_confidence
+from .confidence import depth_match_confidence, depth_match_multi_confidence, match_confidence
 
 _IMAGENET_MEAN = (0.485, 0.456, 0.406)
 _IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -551,6 +551,94 @@ class UniMatch(nn.Module):
         conf = {}
         out = dict(self._forward_batch(img0, img1, 1, confidence=conf, peak_radius=peak_radius, **forward_kw))
         out['depth_confidence'] = conf
+        return out
+
+    def _sweep_multiview(self, ops, tok0, tok1, h, w, cam, cand, sources, use, from_argmax, scale, confidence, peak_radius):
+        """The fused plane sweep of ``sources`` views per reference frame (tokens and ``cam`` source-major, ``[sources * B, ...]``):
+        ``[B, 1, h, w]``.  CUDA tensors: one ``um_depth_corr_softmax_multi`` launch, which also writes the statistics when a
+        ``confidence`` dict asks for them.  Host tensors: ``confidence.depth_match_logits_multi_host``.  One view that is on everywhere
+        is the two-view sweep exactly as :meth:`forward` launches it (the fused launch at S = 1 always reduces the statistics and
+        costs 1.09 x the plain one, profiles/depth_multiview.txt)."""
+        b = tok0.shape[0] // sources
+        f0, f1 = (t.contiguous().view(sources, b, h * w, t.shape[-1]) for t in (tok0, tok1))
+        cams = cam.view(sources, b, 30)
+        if confidence is not None:
+            if sources == 1 and use is None:              # one view, on everywhere: the two-view sweep, as forward launches it
+                out, conf = depth_match_confidence(ops, tok0, tok1, h, w, cam, cand, from_argmax, scale, peak_radius)
+            else:
+                out, conf = depth_match_multi_confidence(ops if tok0.is_cuda else None, f0, f1, h, w, cams, cand, use, from_argmax, scale,
+                                                         peak_radius)
+            confidence.update(conf)
+            return out
+        if sources == 1 and use is None:
+            return ops.depth_corr_softmax(tok0, tok1, h, w, cam, cand, from_argmax)
+        if tok0.is_cuda:
+            return ops.depth_corr_softmax(f0, f1, h, w, cams, cand, from_argmax, use=use)
+        from .confidence import depth_match_multi
+        return depth_match_multi(f0, f1, h, w, cams, cand, use, from_argmax=from_argmax)[0]
+
+    def forward_multiview(self, img_ref, img_srcs, *, intrinsics, poses, attn_type=None, attn_splits_list=None, prop_radius_list=None,
+                          num_reg_refine=1, min_depth=1. / 0.5, max_depth=1. / 10, num_depth_candidates=64, depth_from_argmax=False,
+                          pred_bidir_depth=False, task='depth', return_confidence=False, peak_radius=1):
+        """Depth of ``img_ref [B, 3, H, W]`` from ``S`` source views ``img_srcs [B, S, 3, H, W]`` that vote in ONE plane sweep:
+        ``{'flow_preds': [depth [B, H, W]]}``.  ``intrinsics [B, 3, 3]``, ``poses [B, S, 4, 4]`` = the relative pose reference ->
+        source ``s`` in :meth:`forward`'s convention; the other keywords are :meth:`forward`'s for ``task='depth'``.
+
+        Each of the ``B (1 + S)`` images is encoded once, the Transformer runs on the ``B S`` pairs as one stream (source-major), and
+        the per-source logits are averaged over the sources that see a candidate before the one softmax (``um_depth_corr_softmax_multi``,
+        csrc/depth_multi.hip).  Propagation, upsampling and refinement run on the primary pair ``s = 0`` exactly as in :meth:`forward`.
+        This is an UNLEARNED extension: the weights are trained on two views; the mean over the seeing sources keeps the logits at the
+        scale the softmax was trained at.  With ``S = 1`` the result is that of ``forward(img_ref, img_srcs[:, 0], task='depth', ...)``
+        run as one part.  ``return_confidence=True`` adds ``'depth_confidence'``, the statistics of the FUSED distribution (the keys of
+        :meth:`forward_with_depth_confidence`), from the sweep's own launch.  Depth only, one scale; ``pred_bidir_depth`` is refused (its backward prediction has no second source)."""
+        if task != 'depth':
+            raise ValueError(f"forward_multiview: the plane sweep is the matching step of task='depth', got task={task!r}")
+        if self.num_scales != 1:
+            raise ValueError('forward_multiview needs a one-scale model (num_scales == 1), as task=\'depth\' does')
+        if pred_bidir_depth:
+            raise ValueError('forward_multiview: pred_bidir_depth is a two-view option (the backward prediction has no second source)')
+        if img_srcs.dim() != 5 or img_srcs.shape[0] != img_ref.shape[0] or tuple(img_srcs.shape[2:]) != tuple(img_ref.shape[1:]):
+            raise ValueError(f'img_srcs: expected [B, S, 3, H, W] matching img_ref {tuple(img_ref.shape)}, got {tuple(img_srcs.shape)}')
+        b, sources = img_srcs.shape[:2]
+        if not 1 <= sources <= 8:
+            raise ValueError(f'forward_multiview: 1 .. 8 source views, got {sources}')
+        if tuple(poses.shape) != (b, sources, 4, 4) or tuple(intrinsics.shape) != (b, 3, 3):
+            raise ValueError(f'expected intrinsics [{b}, 3, 3] and poses [{b}, {sources}, 4, 4], got {tuple(intrinsics.shape)} and {tuple(poses.shape)}')
+        if isinstance(peak_radius, bool) or not isinstance(peak_radius, int) or peak_radius < 0:
+            raise ValueError(f'peak_radius: expected an int >= 0, got {peak_radius!r}')
+        if len(attn_splits_list or ()) != 1 or len(prop_radius_list or ()) != 1:
+            raise ValueError('forward_multiview: attn_splits_list and prop_radius_list need one entry (one scale)')
+        ops = self.ops
+        if self.check_weights:
+            self._check_weight_print()
+        dev = img_ref.device
+        if img_ref.is_cuda and self.check_range and getattr(ops, 'mode', 1) == 0:
+            from . import _abi
+            _abi.check_operand_range('an earlier forward of this process: ')
+        import contextlib
+        guard = torch.cuda.device(dev) if img_ref.is_cuda else contextlib.nullcontext()
+        conf = {} if return_confidence else None
+        with guard, torch.no_grad():
+            kw = dict(attn_type=attn_type if attn_type is not None else '', attn_splits_list=attn_splits_list,
+                      prop_radius_list=prop_radius_list, num_reg_refine=num_reg_refine, task='depth', min_depth=min_depth,
+                      max_depth=max_depth, num_depth_candidates=num_depth_candidates, depth_from_argmax=depth_from_argmax,
+                      confidence=conf, peak_radius=peak_radius, sources=sources)
+            if sources == 1:                              # the two-view call: the encoder and the stream of _forward_one
+                img1 = img_srcs[:, 0].contiguous()
+                with_pos = (not self.reg_refine and self.debug_taps is None and getattr(ops, 'fused_glue', False)
+                            and self.backbone.takes_raw_images(ops, img_ref) and img_ref.shape == img1.shape)
+                pos = (lambda h, w: self._position(h, w, attn_splits_list[0], dev)) if with_pos else None
+                feats = self._encode((img_ref, img1), 'depth', pos)
+                out = self._match(feats, b, stream_has_pos=with_pos, intrinsics=intrinsics, pose=poses[:, 0].contiguous(), **kw)
+            else:
+                # every image once: [ref; src_0; ...; src_{S-1}], then the stream of the B S pairs, source-major: [ref x S; sources]
+                feats = self._encode((torch.cat([img_ref, img_srcs.transpose(0, 1).reshape((sources * b,) + tuple(img_ref.shape[1:]))], 0),), 'depth')
+                feats = [torch.cat([f[:b].repeat(sources, 1, 1, 1), f[b:]], 0) for f in feats]
+                out = self._match(feats, sources * b, intrinsics=intrinsics.repeat(sources, 1, 1),
+                                  pose=poses.transpose(0, 1).reshape(sources * b, 4, 4).contiguous(), **kw)
+        out = dict(out)
+        if return_confidence:
+            out['depth_confidence'] = conf
         return out
 
     _PREDICT_DEFAULTS = {'flow': (8, 'sintel', 'flow'), 'stereo': (32, 'sintel', 'disparity'), 'depth': (16, 'kitti', 'depth')}
@@ -1093,15 +1181,20 @@ class UniMatch(nn.Module):
     def _match(self, feats, nb, attn_type='', attn_splits_list=None, corr_radius_list=None, prop_radius_list=None, num_reg_refine=1,
                pred_bidir_flow=False, task='flow', intrinsics=None, pose=None, min_depth=1. / 0.5, max_depth=1. / 10,
                num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, stream_has_pos=False, pred_out=None,
-               confidence=None, peak_radius=1):
+               confidence=None, peak_radius=1, sources=0, use=None):
         """The match step: everything after the encoder, on per-scale features ``feats[s] = [f0; f1]`` (``[2 nb, C, h, w]``, the
         first images of the ``nb`` pairs, then the second ones).  ``stream_has_pos``: the encoder added the position table already
         (``_forward_one`` decides; one scale, no refinement).  ``pred_out``: see ``_forward_one``.  ``confidence``: a dict that receives
         ``confidence.match_confidence`` of the tokens the global matching step (``corr_radius == -1``) matches or, for depth,
-        ``confidence.depth_match_confidence`` of the plane sweep (window ``peak_radius``), whose launch then also writes the prediction."""
+        ``confidence.depth_match_confidence`` of the plane sweep (window ``peak_radius``), whose launch then also writes the prediction.
+        ``sources`` >= 1 (depth, one scale): the ``nb = sources * B`` pairs are ``B`` reference frames with ``sources`` source views each,
+        source-major (``intrinsics`` / ``pose`` likewise); the views vote in ONE plane sweep (``um_depth_corr_softmax_multi``; ``use
+        [sources, B]`` switches views off per sample) and everything after it runs on the primary pairs, the rows ``[:B]``."""
         ops = self.ops
         dev = feats[0].device
         flow, pred = None, None
+        if sources:
+            assert task == 'depth' and self.num_scales == 1 and not pred_bidir_depth and nb % sources == 0
         for s in range(self.num_scales):
             m0, m1 = feats[s][:nb], feats[s][nb:]                         # [B, C, h, w]
             both = None
@@ -1158,7 +1251,14 @@ class UniMatch(nn.Module):
                         pc = torch.cat([pose, torch.inverse(pose)], 0)
                     cam = torch.cat([torch.inverse(kc).flatten(1), pc[:, :3, :3].flatten(1), pc[:, :3, 3],
                                      kc.flatten(1)], 1).float().contiguous()
-                if confidence is not None:
+                if sources:
+                    b = nb // sources
+                    flow_pred = self._sweep_multiview(ops, tok0, tok1, h, w, cam, cand.contiguous(), sources, use, depth_from_argmax, up,
+                                                      confidence, peak_radius)
+                    # propagation, upsampling and refinement run on the primary pair of every reference frame, as in forward
+                    tok0, ori0, ori1, cam = tok0[:b], ori0[:b], ori1[:b], cam[:b]
+                    intrinsics, pose, k_cur = intrinsics[:b], pose[:b], k_cur[:b]
+                elif confidence is not None:
                     flow_pred, conf = depth_match_confidence(ops, f0c, f1c, h, w, cam, cand.contiguous(), depth_from_argmax, up, peak_radius)
                     confidence.update(conf)
                 else:

@@ -1504,13 +1504,24 @@ class HipOps(WorkspaceRegistry):
         _abi.check(code, 'um_prop_local_attn')
         return out
 
-    def depth_corr_softmax(self, f0, f1, h, w, cam, candidates, from_argmax=False, stats=False, peak_radius=1):
+    def depth_corr_softmax(self, f0, f1, h, w, cam, candidates, from_argmax=False, stats=False, peak_radius=1, use=None):
         """cam ``[B, 30]`` = K^-1 | R | t | K (row major), candidates ``[D]`` inverse depths -> ``out [B, 1, h, w]``.
 
         ``stats=True``: the same sweep as ONE ``um_depth_corr_softmax_stats`` launch (recorded as ``'depth_corr_softmax_stats'``) that
         also writes the statistics of the distribution it reduces -> ``(out, stats [B, 4, h, w] = max_prob | entropy | variance |
         peak_mass, index [B, 2, h, w] int32 = best | in_view)``; ``peak_radius``: candidates each side of the best one that count
-        towards ``peak_mass``.  Its memory-contract cases are in tests/test_depth_stats_gpu.py."""
+        towards ``peak_mass``.  Its memory-contract cases are in tests/test_depth_stats_gpu.py.
+
+        Source-major ``f0``, ``f1`` ``[S, B, h*w, 128]`` with ``cam [S, B, 30]``: the S views vote in ONE plane sweep
+        (``um_depth_corr_softmax_multi``, recorded as ``'depth_corr_softmax_multi'``; ``use [S, B]`` switches views off per sample): see
+        :meth:`_depth_corr_softmax_multi`; its memory-contract cases are in tests/test_depth_multiview_gpu.py.  Why one method has two
+        layouts chosen by the rank of ``f0`` instead of a public ``depth_corr_softmax_multi``: the public method list of this class is
+        pinned by tests/test_memory_contract_gpu.py (every public method needs a case or a reason in that file's tables), so a new
+        launch of an existing operation comes in through the existing method, as ``stats=True`` did."""
+        if f0.dim() == 4:
+            return self._depth_corr_softmax_multi(f0, f1, h, w, cam, candidates, use, from_argmax, stats, peak_radius)
+        if use is not None:
+            raise ValueError('use switches source views off: it needs source-major features [S, B, h*w, C]')
         b, l, c = f0.shape
         _check_tokens('f0', f0, tokens=h * w)
         _check_tokens('f1', f1, b, l)
@@ -1533,3 +1544,35 @@ class HipOps(WorkspaceRegistry):
             candidates.numel(), int(bool(from_argmax)), _stream()))
         _abi.check(code, 'um_depth_corr_softmax')
         return out
+
+    def _depth_corr_softmax_multi(self, f0, f1, h, w, cam, candidates, use=None, from_argmax=False, stats=False, peak_radius=1):
+        """:meth:`depth_corr_softmax` for source-major inputs (a private name: the public method is the one entry of the plane sweep).
+        The plane sweep with ``S`` source views voting in one cost volume (``um_depth_corr_softmax_multi``, csrc/depth_multi.hip):
+        source-major ``f0``, ``f1`` ``[S, B, h*w, 128]``, ``cam [S, B, 30]``, ``use [S, B]`` uint8 / bool on the device (0: the source is
+        off for that sample and is never read) or None -> ``out [B, 1, h, w]``; ``stats=True`` -> ``(out, stats [B, 4, h, w], index
+        [B, 2, h, w] int32)`` as :meth:`depth_corr_softmax`.  The logits are averaged over the sources that see a candidate, then one
+        softmax: an unlearned extension.  ONE launch, recorded as ``'depth_corr_softmax_multi'``; no host synchronisation."""
+        if f0.dim() != 4 or not 1 <= f0.shape[0] <= 8:
+            raise ValueError(f'f0: expected source-major [S = 1 .. 8, B, h*w, C], got {tuple(f0.shape)}')
+        s, b, l, c = f0.shape
+        for name, t in (('f0', f0), ('f1', f1)):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (s, b, h * w, c)):
+                raise ValueError(f'{name}: expected a contiguous CUDA float32 [{s}, {b}, {h * w}, {c}] tensor, got '
+                                 f'{tuple(t.shape)} {t.dtype} {t.device} contiguous={t.is_contiguous()}')
+        if not (cam.is_cuda and cam.dtype == torch.float32 and cam.is_contiguous() and tuple(cam.shape) == (s, b, 30)):
+            raise ValueError(f'cam: expected contiguous CUDA float32 [{s}, {b}, 30]')
+        if not (candidates.is_cuda and candidates.dtype == torch.float32 and candidates.is_contiguous()
+                and candidates.dim() == 1):
+            raise ValueError('candidates: expected contiguous CUDA float32 [D]')
+        if use is not None:
+            if not (use.is_cuda and use.dtype in (torch.uint8, torch.bool) and use.is_contiguous() and tuple(use.shape) == (s, b)):
+                raise ValueError(f'use: expected contiguous CUDA uint8 or bool [{s}, {b}]')
+        out = torch.empty((b, 1, h, w), dtype=torch.float32, device=f0.device)
+        planes = torch.empty((b, 4, h, w), dtype=torch.float32, device=f0.device) if stats else None
+        index = torch.empty((b, 2, h, w), dtype=torch.int32, device=f0.device) if stats else None
+        code = self._launch('depth_corr_softmax_multi', lambda: self.lib.um_depth_corr_softmax_multi(
+            _ptr(f0), _ptr(f1), _ptr(cam), _ptr(use) if use is not None else None, _ptr(candidates), _ptr(out),
+            _ptr(planes) if stats else None, _ptr(index) if stats else None, s, b, h, w, c,
+            candidates.numel(), int(bool(from_argmax)), int(peak_radius), _stream()))
+        _abi.check(code, 'um_depth_corr_softmax_multi')
+        return (out, planes, index) if stats else out
