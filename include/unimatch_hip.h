@@ -42,7 +42,7 @@ extern "C" {
 #endif
 
 #define UM_VERSION 220   /* 220 also gained um_global_match_stats_workspace_bytes, um_global_match_stats and um_match_mutual,
-                            um_depth_corr_softmax_multi */
+                            um_depth_corr_softmax_multi, um_depth_corr_softmax_multi_rows */
 
 #define UM_MODE_EXACT 0
 #define UM_MODE_FAST 1
@@ -607,6 +607,25 @@ int um_depth_corr_softmax_multi(const float* f0, const float* f1, const float* c
                                 const float* candidates, float* out, float* stats, int* index,
                                 int sources, int batch, int h, int w, int channels, int num_candidates,
                                 int from_argmax, int peak_radius, void* stream);
+
+/* um_depth_corr_softmax_multi on operands that are ROWS of other tensors, named by a table instead of copied into the source-major
+ * layout: the same fusion rule, arithmetic, outputs and kernel forms, bit for bit the contiguous entry's result on the same operands.
+ *   segments      HOST array of num_segments (1 .. 4) device pointers, segment i = [segment_rows[i], h*w, 128] fp32;
+ *   segment_rows  HOST int array.  A token row index addresses the concatenation of the segments in order.  Both arrays are read
+ *                 before the call returns; the table reaches the kernel by value in its arguments.
+ *   cam [cam_rows, 30], candidates [D],
+ *   rows [S, B, 3] int32 on the DEVICE = f0 row | f1 row | cam row of source s for sample b.  The host does not inspect it.  A source
+ *                 any of whose three indices is negative or out of range (>= the segments' total rows, >= cam_rows for the cam row)
+ *                 is OFF for that sample and is never read -- the `use` of the contiguous entry, and what keeps a bad table from
+ *                 reading out of bounds.  A sample whose sources are all off gets the uniform distribution, in_view 0.
+ *   out, stats, index, from_argmax, peak_radius, stream: as above.
+ * Errors (negative, nothing launched): a null segments / segment_rows / cam / rows / candidates / out, a null segment pointer or
+ * segment_rows[i] <= 0, num_segments outside 1 .. 4, cam_rows <= 0, channels != 128, num_candidates outside 1 .. 128, sources outside
+ * 1 .. 8, peak_radius < 0. */
+int um_depth_corr_softmax_multi_rows(const float* const* segments, const int* segment_rows, int num_segments,
+                                     const float* cam, int cam_rows, const int* rows, const float* candidates,
+                                     float* out, float* stats, int* index, int sources, int batch, int h, int w, int channels,
+                                     int num_candidates, int from_argmax, int peak_radius, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * RAFT convex upsampling (SURVEY.md 8(f) "next" row): softmax over the 9 neighbours of each of factor^2 sub-pixels,

@@ -135,6 +135,7 @@ SIGNATURES = {
     'um_depth_corr_softmax': (_c_int, [_c_void_p] * 5 + [_c_int] * 6 + [_c_void_p]),
     'um_depth_corr_softmax_stats': (_c_int, [_c_void_p] * 7 + [_c_int] * 7 + [_c_void_p]),
     'um_depth_corr_softmax_multi': (_c_int, [_c_void_p] * 8 + [_c_int] * 8 + [_c_void_p]),
+    'um_depth_corr_softmax_multi_rows': (_c_int, [_c_void_p] * 2 + [_c_int, _c_void_p, _c_int] + [_c_void_p] * 5 + [_c_int] * 8 + [_c_void_p]),
     'um_census_enable': (_c_int, [_c_int]),
     'um_census_count': (ctypes.c_long, [_c_int]),
     'um_window_attn_tile_census': (_c_int, [_c_int, ctypes.POINTER(ctypes.c_ulonglong)]),

@@ -43,7 +43,9 @@ RESOURCE_GUARDS = {'conv.hip': {'conv_entry_kernel': 2},
                    'local_ops.hip': {'depth_corr_softmax_kernel': 3, 'depth_corr_softmax_box_kernel': 3, 'depth_corr_softmax_stats_kernel': 3,
                                      'depth_corr_softmax_box_stats_kernel': 3},
                    # the multi-view plane sweep: the same table and the same three waves as K7's box form, no scratch
-                   'depth_multi.hip': {'depth_multi_box_kernel': 3, 'depth_multi_gather_kernel': 3},
+                   # (the row-table kernels are the same two bodies with another operand addressing)
+                   'depth_multi.hip': {'depth_multi_box_kernel': 3, 'depth_multi_gather_kernel': 3,
+                                       'depth_multi_rows_box_kernel': 3, 'depth_multi_rows_gather_kernel': 3},
                    # memory-bound per-pixel kernels: no scratch, and registers far below what would cost a wave
                    'geometry.hip': {'disp_consistency_kernel': 4, 'depth_consistency_kernel': 4, 'points_count_kernel': 4,
                                     'points_scan_kernel': 4, 'points_scatter_kernel': 4},

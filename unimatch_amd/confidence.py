@@ -35,7 +35,9 @@ run ``depth_match_prob_host`` / ``depth_stats_from_prob_host``, the reference's 
 
   depth_match_multi(f0, f1, h, w, cam, candidates, use=)          several source views ``[S, B, ...]`` vote in one sweep: the logits are
                                                                   averaged over the sources that see a candidate, then one softmax
-                                                                  (``um_depth_corr_softmax_multi``; unlearned, the weights know two views)
+                                                                  (``um_depth_corr_softmax_multi``; unlearned, the weights know two views);
+                                                                  ``rows=``: the operands are rows of other tensors, named by a table
+                                                                  and not copied (``um_depth_corr_softmax_multi_rows``)
 """
 from collections import namedtuple
 
@@ -334,7 +336,30 @@ def _check_multi_inputs(f0, f1, h, w, cam, candidates, use):
         raise ValueError(f'use: expected [{f0.shape[0]}, {f0.shape[1]}] on {f0.device}, got {tuple(use.shape)} on {use.device}')
 
 
-def depth_match_logits_multi_host(f0, f1, h, w, cam, candidates, use=None):
+def depth_rows_to_source_major_host(segments, cam, rows):
+    """The operands a row table names, copied into the source-major layout: ``(f0, f1 [S, B, h*w, C], cam [S, B, 30], use [S, B]
+    bool)``.  ``segments``: 1 .. 4 token tensors ``[n_i, h*w, C]`` (a token row indexes their concatenation in order), ``cam [Rc, 30]``,
+    ``rows [S, B, 3]`` integer = f0 row | f1 row | cam row.  A source with a negative or too-large index is off (``use`` false): its
+    operands in the result are placeholders that nothing reads.  Works on any device; on the GPU this copy is what the row-table launch
+    exists to avoid."""
+    if torch.is_tensor(segments) or not 1 <= len(segments) <= 4:
+        raise ValueError('rows: f0 must be a tuple or list of 1 .. 4 token tensors (the segments)')
+    if any(t.dim() != 3 or t.shape[1:] != segments[0].shape[1:] or t.shape[0] < 1 or t.dtype != segments[0].dtype
+           or t.device != segments[0].device for t in segments):
+        raise ValueError(f'segments: expected [n_i >= 1, h*w, C] tensors of one dtype and device, got {[tuple(t.shape) for t in segments]}')
+    if cam.dim() != 2 or cam.shape[0] < 1 or cam.shape[1] != 30:
+        raise ValueError(f'cam: expected [Rc >= 1, 30] with a row table, got {tuple(cam.shape)}')
+    if rows.dim() != 3 or not 1 <= rows.shape[0] <= 8 or rows.shape[2] != 3 or rows.is_floating_point():
+        raise ValueError(f'rows: expected integer [S = 1 .. 8, B, 3] = f0 row | f1 row | cam row, got {tuple(rows.shape)} {rows.dtype}')
+    tokens = segments[0] if len(segments) == 1 else torch.cat(list(segments), 0)
+    idx = rows.long()
+    total, cam_rows = tokens.shape[0], cam.shape[0]
+    use = (idx >= 0).all(-1) & (idx[..., 0] < total) & (idx[..., 1] < total) & (idx[..., 2] < cam_rows)
+    idx = torch.where(use[..., None], idx, torch.zeros_like(idx))
+    return tokens[idx[..., 0]], tokens[idx[..., 1]], cam[idx[..., 2]], use
+
+
+def depth_match_logits_multi_host(f0, f1, h, w, cam, candidates, use=None, rows=None):
     """The fused logits of the multi-view plane sweep (``um_depth_corr_softmax_multi``), in the dtype of the inputs.  ``f0``, ``f1``
     ``[S, B, h*w, C]``, ``cam [S, B, 30]``, ``use [S, B]`` (false: the source is off for that sample and is not read) or None.  With
     ``l_sj`` the logit and ``v_sj`` the visibility of :func:`depth_match_logits_visible_host` for source ``s``:
@@ -342,7 +367,14 @@ def depth_match_logits_multi_host(f0, f1, h, w, cam, candidates, use=None):
         ``n_j = sum_s v_sj``,   ``l_j = (sum_s v_sj l_sj) / max(1, n_j)``
 
     -- a mean over the sources that see the candidate (an unlearned extension: the weights are trained on two views).  Returns
-    ``(logits [B, D, h, w], in_view [B, h, w] int32 = candidates with n_j >= 1, views [B, D, h, w] int32 = n_j)``."""
+    ``(logits [B, D, h, w], in_view [B, h, w] int32 = candidates with n_j >= 1, views [B, D, h, w] int32 = n_j)``.
+
+    With ``rows [S, B, 3]`` (``um_depth_corr_softmax_multi_rows``): ``f0`` is the tuple or list of segments, ``f1`` None, ``cam [Rc, 30]``;
+    the rows are gathered into the source-major layout (:func:`depth_rows_to_source_major_host`) and an off source is ``use`` false."""
+    if rows is not None:
+        if f1 is not None or use is not None:
+            raise ValueError('rows names every operand: f1 must be None (f0 holds the segments) and use must be None')
+        f0, f1, cam, use = depth_rows_to_source_major_host(f0, cam, rows)
     _check_multi_inputs(f0, f1, h, w, cam, candidates, use)
     s_count, b = f0.shape[:2]
     d = candidates.numel()
@@ -360,23 +392,37 @@ def depth_match_logits_multi_host(f0, f1, h, w, cam, candidates, use=None):
     return fused, (views >= 1).sum(1).to(torch.int32), views
 
 
-def depth_match_stats_multi_host(f0, f1, h, w, cam, candidates, use=None, peak_radius=1):
+def depth_match_stats_multi_host(f0, f1, h, w, cam, candidates, use=None, peak_radius=1, rows=None):
     """``DepthMatchStats`` of the fused distribution ``softmax_j l_j`` of :func:`depth_match_logits_multi_host`, which it forms."""
-    logits, seen, _ = depth_match_logits_multi_host(f0, f1, h, w, cam, candidates, use)
+    logits, seen, _ = depth_match_logits_multi_host(f0, f1, h, w, cam, candidates, use, rows)
     return depth_stats_from_prob_host(torch.softmax(logits, 1), candidates, seen, peak_radius)
 
 
-def depth_match_multi(f0, f1, h, w, cam, candidates, use=None, *, from_argmax=False, peak_radius=1, ops=None):
+def depth_match_multi(f0, f1, h, w, cam, candidates, use=None, *, from_argmax=False, peak_radius=1, ops=None, rows=None):
     """The multi-view plane sweep: ``(out [B, 1, h, w], DepthMatchStats)`` of the source-major ``f0``, ``f1`` ``[S, B, h*w, 128]`` under
     ``cam [S, B, 30]`` over the inverse-depth ``candidates [D]``; ``use [S, B]`` switches sources off per sample.  ``out`` is the
     soft-argmin of the fused distribution (``from_argmax``: the candidate at ``best``).  CUDA tensors run ONE
     ``um_depth_corr_softmax_multi`` launch (through ``ops``, a ``HipOps``, when given: its launch record sees the call); host tensors
-    run the restatement above.  There is no fallback from one to the other.  The fusion is unlearned: see csrc/depth_multi.hip."""
-    _check_multi_inputs(f0, f1, h, w, cam, candidates, use)
+    run the restatement above.  There is no fallback from one to the other.  The fusion is unlearned: see csrc/depth_multi.hip.
+
+    ``rows [S, B, 3]`` int32 = f0 row | f1 row | cam row: the operands are rows of other tensors, named and not copied.  ``f0`` is then
+    a tuple or list of 1 .. 4 token tensors ``[n_i, h*w, 128]`` (the segments; a token row indexes their concatenation), ``f1`` and
+    ``use`` are None and ``cam`` is ``[Rc, 30]``; a source with a negative or too-large index is off for that sample.  CUDA tensors run
+    ONE ``um_depth_corr_softmax_multi_rows`` launch, bit for bit the contiguous launch on the gathered operands; host tensors gather
+    the rows and run the same restatement."""
     if int(peak_radius) < 0:
         raise ValueError(f'peak_radius must be >= 0, got {peak_radius}')
-    if not f0.is_cuda:
-        logits, seen, _ = depth_match_logits_multi_host(f0, f1, h, w, cam, candidates, use)
+    if rows is not None:
+        if f1 is not None or use is not None:
+            raise ValueError('rows names every operand: f1 must be None (f0 holds the segments) and use must be None')
+        if torch.is_tensor(f0) or not 1 <= len(f0) <= 4:
+            raise ValueError('rows: f0 must be a tuple or list of 1 .. 4 token tensors (the segments)')
+        is_cuda = f0[0].is_cuda
+    else:
+        _check_multi_inputs(f0, f1, h, w, cam, candidates, use)
+        is_cuda = f0.is_cuda
+    if not is_cuda:
+        logits, seen, _ = depth_match_logits_multi_host(f0, f1, h, w, cam, candidates, use, rows)
         prob = torch.softmax(logits, 1)
         st = depth_stats_from_prob_host(prob, candidates, seen, int(peak_radius))
         cand = candidates.to(prob.dtype)
@@ -385,13 +431,15 @@ def depth_match_multi(f0, f1, h, w, cam, candidates, use=None, *, from_argmax=Fa
     if ops is None:
         from .ops import HipOps              # raises when the HIP extension is missing: there is no silent fallback
         ops = HipOps('exact')
-    out, stats, index = ops.depth_corr_softmax(f0, f1, h, w, cam, candidates, from_argmax, stats=True, peak_radius=int(peak_radius), use=use)
+    out, stats, index = ops.depth_corr_softmax(f0, f1, h, w, cam, candidates, from_argmax, stats=True, peak_radius=int(peak_radius), use=use,
+                                               **({} if rows is None else {'rows': rows}))
     return out, DepthMatchStats(stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3], index[:, 0], index[:, 1])
 
 
-def depth_match_multi_confidence(ops, f0, f1, h, w, cam, candidates, use, from_argmax, scale, peak_radius=1):
-    """The fused sweep's prediction and its ``'depth_confidence'`` dict (the keys of :func:`depth_match_confidence`)."""
-    out, s = depth_match_multi(f0, f1, h, w, cam, candidates, use, from_argmax=from_argmax, peak_radius=peak_radius, ops=ops)
+def depth_match_multi_confidence(ops, f0, f1, h, w, cam, candidates, use, from_argmax, scale, peak_radius=1, rows=None):
+    """The fused sweep's prediction and its ``'depth_confidence'`` dict (the keys of :func:`depth_match_confidence`); ``rows``: the
+    operands by row table, as in :func:`depth_match_multi`."""
+    out, s = depth_match_multi(f0, f1, h, w, cam, candidates, use, from_argmax=from_argmax, peak_radius=peak_radius, ops=ops, rows=rows)
     return out, dict(s._asdict(), scale=int(scale), num_candidates=int(candidates.numel()))
 
 

@@ -1,6 +1,7 @@
 // Multi-view plane sweep: several source views vote in ONE cost volume before the softmax.   gfx950 / wave64
 //
-//   um_depth_corr_softmax_multi   S source views, one reference pixel grid, one candidate list -> soft-argmin + statistics
+//   um_depth_corr_softmax_multi        S source views, one reference pixel grid, one candidate list -> soft-argmin + statistics
+//   um_depth_corr_softmax_multi_rows   the same with the operands named by a row table (further down)
 //
 // The fusion rule.  Sources s = 0 .. S-1 share the reference pixel p and the inverse-depth candidates c_j; use[s, b] = 0 switches a
 // source off for a sample (it is then never read).  For a source that is on,
@@ -398,6 +399,253 @@ __global__ __launch_bounds__(256) void depth_multi_gather_kernel(const float* __
     }
 }
 
+// ====================================================================================================== operands by row table
+//   um_depth_corr_softmax_multi_rows   the same sweep on operands that are ROWS of other tensors (the Transformer's output stream of a
+//                                      video chunk), named by a table instead of copied into the source-major layout
+// rows [S, B, 3] int32 = f0 row | f1 row | cam row of source s for sample b.  A token row addresses the concatenation of up to
+// DEPTH_MAX_SEGMENTS segments [n_i, L, 128]; a cam row addresses cam [cam_rows, 30].  A source any of whose three indices is negative or
+// past the end is OFF for the sample and is never read (the `use` of the contiguous entry, and what keeps a bad table in bounds).
+// The segment table is a kernel argument, passed by value: first_i is the first row of segment i (INT_MAX for a segment that is not
+// there), so the segment of a row is a chain of scalar compares and selects on values read with readfirstlane -- a wave works on one
+// pixel, so the three indices are the same in every lane and the base pointers stay in scalar registers.
+// The two kernels below are the two kernels above with this addressing, statement for statement: every device function is shared, the
+// arithmetic and its order are the same, the results agree bit for bit (tests/test_depth_fuse_neighbours_gpu.py).  They are separate
+// kernels and not instantiations of one template because moving the bodies above into templates changed the instructions of
+// depth_multi_box_kernel and depth_multi_gather_kernel, whose rounding test_one_source_is_the_two_view_kernel pins.
+#define DEPTH_MAX_SEGMENTS 4
+struct DepthSegments {                                           // plain members, no arrays: nothing to index, nothing in scratch
+    const float *ptr0, *ptr1, *ptr2, *ptr3;
+    int first1, first2, first3;
+    int total;                                                   // rows of all segments
+};
+
+struct DepthSource { const float* cm; const float* f1b; const float* f0b; };     // cam record, first row of the f1 and f0 samples
+
+__device__ __forceinline__ const float* depth_segment_row(const DepthSegments& seg, int r, int L) {      // 0 <= r < seg.total, uniform
+    const float* base = seg.ptr0;
+    int first = 0;
+    if (r >= seg.first1) { base = seg.ptr1; first = seg.first1; }
+    if (r >= seg.first2) { base = seg.ptr2; first = seg.first2; }
+    if (r >= seg.first3) { base = seg.ptr3; first = seg.first3; }
+    return base + (long)(r - first) * L * UM_CHANNELS;
+}
+
+__device__ __forceinline__ bool depth_source_rows(const DepthSegments& seg, const float* __restrict__ cam, const int* __restrict__ rows,
+                                                  int cam_rows, int s, int b, int batch, int L, DepthSource& o) {
+    const int* r = rows + ((long)s * batch + b) * 3;
+    const int r0 = __builtin_amdgcn_readfirstlane(r[0]), r1 = __builtin_amdgcn_readfirstlane(r[1]);
+    const int rc = __builtin_amdgcn_readfirstlane(r[2]);
+    if (r0 < 0 || r1 < 0 || rc < 0 || r0 >= seg.total || r1 >= seg.total || rc >= cam_rows) return false;
+    o.cm = cam + (long)rc * 30;
+    o.f1b = depth_segment_row(seg, r1, L);
+    o.f0b = depth_segment_row(seg, r0, L);
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------- row table, D <= 64: lane = candidate
+__global__ __launch_bounds__(256) void depth_multi_rows_box_kernel(const DepthSegments seg, const float* __restrict__ cam,
+                                                                   const int* __restrict__ rows, int cam_rows,
+                                                                   const float* __restrict__ cand, float* __restrict__ out,
+                                                                   float* __restrict__ stats, int* __restrict__ index, int sources,
+                                                                   int batch, int h, int w, int nd, int from_argmax, int peak_radius) {
+    __shared__ float tab_all[4][DEPTH_BOX];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int slot = lane >> 2, quarter = lane & 3;
+    float* tab = tab_all[wave];
+    const int L = h * w;
+    const long total = (long)batch * L;
+    const float scale = 1.0f / sqrtf((float)UM_CHANNELS);
+    // the lane's candidate does not depend on the pixel or the source
+    const bool tap = lane < nd;
+    const float ci = cand[tap ? lane : 0];
+    const float depth = 1.0f / ci;
+    const int rounds = (nd + 15) >> 4;                           // of the gather form: at most 4
+    for (long pid = (long)blockIdx.x * 4 + wave; pid < total; pid += (long)gridDim.x * 4) {
+        const int b = (int)(pid / L), p = (int)(pid - (long)b * L);
+        const int y = p / w, x = p - y * w;
+        float acc = 0.f;                                         // sum_s v_sj l_sj of the lane's candidate
+        int cnt = 0;                                             // n_j
+        bool gathered = false;                                   // wave-uniform: a source of this pixel took the gather form
+        for (int s = 0; s < sources; ++s) {
+            DepthSource src;
+            if (!depth_source_rows(seg, cam, rows, cam_rows, s, b, batch, L, src)) continue;     // wave-uniform; off: never read
+            const float* cm = src.cm;
+            const float* f1b = src.f1b;
+            const DepthRay q = depth_ray(cm, x, y);
+            const DepthTap t = depth_tap(cm, q, depth);
+            // bounding box of the corners that can lie inside the image: a candidate whose x0 is outside [-1, w-1] has no corner in it
+            const int cx0 = min(max(t.x0, -1), w - 1), cy0 = min(max(t.y0, -1), h - 1);
+            const int bx0 = wave_min_i(tap ? cx0 : 0x7fffffff), bx1 = wave_max_i(tap ? cx0 + 1 : -0x7fffffff);
+            const int by0 = wave_min_i(tap ? cy0 : 0x7fffffff), by1 = wave_max_i(tap ? cy0 + 1 : -0x7fffffff);
+            const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
+            const int npos = bw * bh;
+            f32x4 a[8];
+            load32(a, src.f0b + (long)p * UM_CHANNELS + 4 * quarter);
+            float lg;
+            bool seen;                                           // v_sj, from the tap that formed l_sj
+            if (npos > DEPTH_BOX) {                              // wave-uniform: this source by plain gathers, 16 candidates per round
+                gathered = true;
+                for (int r = 0; r < rounds; ++r) {
+                    const int tt = r * 16 + slot;
+                    const bool on = tt < nd;
+                    const DepthTap g = depth_tap_slots(cm, q, 1.0f / cand[on ? tt : 0]);
+                    float d = 0.f;
+                    if (on) d = depth_tap_gather(a, f1b, g, h, w, quarter);
+                    d = quad_sum(d);
+                    if (quarter == 0 && on) {                    // tt < nd <= 64 and 64 + tt < 128 <= DEPTH_BOX
+                        tab[tt] = depth_logit(d, scale);
+                        tab[64 + tt] = depth_tap_seen(g, h, w) ? 1.f : 0.f;     // v_sj of the tap the logit was gathered at, as K7 counts it
+                    }
+                }
+                lds_settle();
+                lg = tab[tap ? lane : 0];
+                seen = tap && tab[64 + (tap ? lane : 0)] != 0.f;
+            } else {
+                const float rbw = 1.0f / (float)bw;
+                for (int i0 = 0; i0 < npos; i0 += 16) {
+                    const int i = i0 + slot;
+                    int ry = (int)((float)i * rbw);               // i / bw for 0 <= i < 160, corrected below
+                    ry += ((ry + 1) * bw <= i) ? 1 : 0;
+                    ry -= (ry * bw > i) ? 1 : 0;
+                    const int py = by0 + ry, px = bx0 + (i - ry * bw);
+                    float d = 0.f;
+                    if (i < npos && py >= 0 && py < h && px >= 0 && px < w)
+                        d = dot32(a, f1b + (long)(py * w + px) * UM_CHANNELS + 4 * quarter);
+                    d = quad_sum(d);
+                    if (quarter == 0 && i < npos) tab[i] = d;
+                }
+                lds_settle();                                    // the table is complete
+                float d = 0.f;
+                if (tap) {
+#pragma unroll
+                    for (int cy = 0; cy < 2; ++cy)
+#pragma unroll
+                        for (int cx = 0; cx < 2; ++cx) {
+                            const int yy = t.y0 + cy, xx = t.x0 + cx;
+                            if (yy >= 0 && yy < h && xx >= 0 && xx < w) {
+                                const float wt = (cx ? t.wx : 1.f - t.wx) * (cy ? t.wy : 1.f - t.wy);
+                                d += wt * tab[(yy - by0) * bw + (xx - bx0)];
+                            }
+                        }
+                }
+                lg = depth_logit(d, scale);
+                seen = tap && depth_tap_seen(t, h, w);
+            }
+            lds_settle();                                        // every lane has read before the next source overwrites the table
+            acc += seen ? lg : 0.f;
+            cnt += seen ? 1 : 0;
+        }
+        const float fused = acc / (float)max(cnt, 1);
+        const int in_view = __popcll(__ballot(tap && cnt >= 1));
+        float res;
+        DepthPixelStats st;
+        if (gathered) {                                          // the order of K7's gather form: slots x rounds
+            if (tap) tab[lane] = fused;
+            lds_settle();
+            float logit[4], cv[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int tt = r * 16 + slot;
+                const bool on = r < rounds && tt < nd;
+                logit[r] = on ? tab[tt] : -3.0e38f;
+                cv[r] = r < rounds ? cand[on ? tt : 0] : 0.f;
+            }
+            lds_settle();
+            res = depth_softmax_slots<4>(logit, cv, rounds, nd, slot, cand, from_argmax, peak_radius, st);
+        } else {                                                 // the order of K7's box form: one candidate per lane
+            const float logit = tap ? fused : -3.0e38f;
+            const float mx = wave_max_f(logit);
+            const float e = tap ? __expf(logit - mx) : 0.f;
+            const float sp = wave_sum_f(e), sc = wave_sum_f(e * ci);
+            res = sc / sp;
+            const int mi = wave_min_i((tap && logit == mx) ? lane : 0x7fffffff);     // first index attaining the maximum
+            const float dc = ci - res;
+            const float sl = wave_sum_f(tap ? e * (logit - mx) : 0.f);
+            const float sv = wave_sum_f(e * (dc * dc));
+            const float sm = wave_sum_f(abs(lane - mi) <= peak_radius ? e : 0.f);
+            st.max_prob = 1.0f / sp;
+            st.entropy = fmaxf(depth_ln(sp) - sl / sp, 0.f);
+            st.variance = sv / sp;
+            st.peak_mass = sm / sp;
+            st.best = mi;
+            if (from_argmax) res = cand[mi];
+        }
+        st.in_view = in_view;
+        if (lane == 0) {
+            out[pid] = res;
+            depth_stats_store(stats, index, b, p, L, st);
+        }
+    }
+}
+
+// ----------------------------------------------------------------------------- row table, D > 64: 16 slots x 4 channel quarters
+__global__ __launch_bounds__(256) void depth_multi_rows_gather_kernel(const DepthSegments seg, const float* __restrict__ cam,
+                                                                      const int* __restrict__ rows, int cam_rows,
+                                                                      const float* __restrict__ cand, float* __restrict__ out,
+                                                                      float* __restrict__ stats, int* __restrict__ index, int sources,
+                                                                      int batch, int h, int w, int nd, int from_argmax, int peak_radius) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int slot = lane >> 2, quarter = lane & 3;
+    const int L = h * w;
+    const long total = (long)batch * L;
+    const int rounds = (nd + 15) >> 4;
+    const float scale = 1.0f / sqrtf((float)UM_CHANNELS);
+    float cv[LOCAL_MAX_ROUNDS], dep[LOCAL_MAX_ROUNDS];           // the slot's candidates and their depths: the same for every pixel
+#pragma unroll
+    for (int r = 0; r < LOCAL_MAX_ROUNDS; ++r) {
+        const int t = r * 16 + slot;
+        cv[r] = r < rounds ? cand[t < nd ? t : 0] : 0.f;
+        dep[r] = r < rounds ? 1.0f / cv[r] : 0.f;
+    }
+    for (long pid = (long)blockIdx.x * 4 + wave; pid < total; pid += (long)gridDim.x * 4) {
+        const int b = (int)(pid / L), p = (int)(pid - (long)b * L);
+        const int y = p / w, x = p - y * w;
+        float acc[LOCAL_MAX_ROUNDS];
+        int cnt[LOCAL_MAX_ROUNDS];
+#pragma unroll
+        for (int r = 0; r < LOCAL_MAX_ROUNDS; ++r) { acc[r] = 0.f; cnt[r] = 0; }
+        for (int s = 0; s < sources; ++s) {
+            DepthSource src;
+            if (!depth_source_rows(seg, cam, rows, cam_rows, s, b, batch, L, src)) continue;     // wave-uniform; off: never read
+            const float* cm = src.cm;
+            const float* f1b = src.f1b;
+            const DepthRay q = depth_ray_slots(cm, x, y);
+            f32x4 a[8];
+            load32(a, src.f0b + (long)p * UM_CHANNELS + 4 * quarter);
+#pragma unroll
+            for (int r = 0; r < LOCAL_MAX_ROUNDS; ++r) {
+                if (r < rounds) {
+                    const bool on = r * 16 + slot < nd;
+                    const DepthTap t = depth_tap_slots(cm, q, dep[r]);
+                    float d = 0.f;
+                    if (on) d = depth_tap_gather(a, f1b, t, h, w, quarter);
+                    d = quad_sum(d);
+                    const bool seen = on && depth_tap_seen(t, h, w);
+                    acc[r] += seen ? depth_logit(d, scale) : 0.f;
+                    cnt[r] += seen ? 1 : 0;
+                }
+            }
+        }
+        int seen_any = 0;
+#pragma unroll
+        for (int r = 0; r < LOCAL_MAX_ROUNDS; ++r) {
+            if (r < rounds) {
+                seen_any += cnt[r] >= 1 ? 1 : 0;
+                acc[r] = r * 16 + slot < nd ? acc[r] / (float)max(cnt[r], 1) : -3.0e38f;
+            } else {
+                acc[r] = -3.0e38f;
+            }
+        }
+        DepthPixelStats st;
+        const float res = depth_softmax_slots<LOCAL_MAX_ROUNDS>(acc, cv, rounds, nd, slot, cand, from_argmax, peak_radius, st);
+        st.in_view = slot_sum_i(seen_any);
+        if (lane == 0) {
+            out[pid] = res;
+            depth_stats_store(stats, index, b, p, L, st);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------ host side
 extern void um_set_error(const char* fmt, ...);
 
@@ -434,5 +682,72 @@ extern "C" int um_depth_corr_softmax_multi(const float* f0, const float* f1, con
     else
         hipLaunchKernelGGL(depth_multi_gather_kernel, grid, dim3(256), 0, (hipStream_t)stream, f0, f1, cam, use, candidates, out, stats,
                            index, sources, batch, h, w, num_candidates, from_argmax, peak_radius);
+    return (int)hipGetLastError();
+}
+
+extern "C" int um_depth_corr_softmax_multi_rows(const float* const* segments, const int* segment_rows, int num_segments,
+                                                const float* cam, int cam_rows, const int* rows, const float* candidates, float* out,
+                                                float* stats, int* index, int sources, int batch, int h, int w, int channels,
+                                                int num_candidates, int from_argmax, int peak_radius, void* stream) {
+    if (!segments || !segment_rows || !cam || !rows || !candidates || !out || batch <= 0 || h <= 0 || w <= 0) {
+        um_set_error("um_depth_corr_softmax_multi_rows: null pointer or non-positive size (segments=%p segment_rows=%p cam=%p rows=%p candidates=%p out=%p batch=%d h=%d w=%d)",
+                     (const void*)segments, (const void*)segment_rows, (const void*)cam, (const void*)rows, (const void*)candidates,
+                     (const void*)out, batch, h, w);
+        return -1;
+    }
+    if (num_segments < 1 || num_segments > DEPTH_MAX_SEGMENTS) {
+        um_set_error("num_segments=%d unsupported (1..%d)", num_segments, DEPTH_MAX_SEGMENTS);
+        return -4;
+    }
+    if (cam_rows <= 0) {
+        um_set_error("cam_rows=%d: the cam table needs at least one row", cam_rows);
+        return -4;
+    }
+    if (channels != UM_CHANNELS) {
+        um_set_error("channels=%d unsupported (the library is built for %d)", channels, UM_CHANNELS);
+        return -1;
+    }
+    if (sources < 1 || sources > 8) {
+        um_set_error("sources=%d unsupported (1..8)", sources);
+        return -4;
+    }
+    if (num_candidates < 1 || num_candidates > 16 * LOCAL_MAX_ROUNDS) {
+        um_set_error("num_candidates=%d unsupported (1..%d)", num_candidates, 16 * LOCAL_MAX_ROUNDS);
+        return -4;
+    }
+    if (peak_radius < 0) {
+        um_set_error("peak_radius=%d: the window around the best candidate needs a radius >= 0", peak_radius);
+        return -4;
+    }
+    const float* ptr[DEPTH_MAX_SEGMENTS];
+    int first[DEPTH_MAX_SEGMENTS];
+    long total_rows = 0;
+    for (int i = 0; i < DEPTH_MAX_SEGMENTS; ++i) {
+        ptr[i] = nullptr;
+        first[i] = 0x7fffffff;                                   // no row index reaches a segment that is not there
+        if (i >= num_segments) continue;
+        if (!segments[i] || segment_rows[i] <= 0) {
+            um_set_error("segment %d: pointer %p with %d rows (every segment needs a pointer and at least one row)", i,
+                         (const void*)segments[i], segment_rows[i]);
+            return -4;
+        }
+        ptr[i] = segments[i];
+        first[i] = (int)total_rows;
+        total_rows += segment_rows[i];
+        if (total_rows >= 0x7fffffff) {
+            um_set_error("the segments hold %ld rows or more: a row index is a 32-bit int", total_rows);
+            return -4;
+        }
+    }
+    DepthSegments seg = {ptr[0], ptr[1], ptr[2], ptr[3], first[1], first[2], first[3], 0};
+    seg.total = (int)total_rows;
+    ScopedKernelTimer timer(UM_K_DEPTH_CORR, (hipStream_t)stream);
+    const dim3 grid(pixel_grid_blocks((long)batch * h * w));
+    if (num_candidates <= 64)
+        hipLaunchKernelGGL(depth_multi_rows_box_kernel, grid, dim3(256), 0, (hipStream_t)stream, seg, cam, rows, cam_rows, candidates, out,
+                           stats, index, sources, batch, h, w, num_candidates, from_argmax, peak_radius);
+    else
+        hipLaunchKernelGGL(depth_multi_rows_gather_kernel, grid, dim3(256), 0, (hipStream_t)stream, seg, cam, rows, cam_rows, candidates,
+                           out, stats, index, sources, batch, h, w, num_candidates, from_argmax, peak_radius);
     return (int)hipGetLastError();
 }

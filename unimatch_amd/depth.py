@@ -12,7 +12,9 @@ intrinsics; ``--scale-intrinsics`` opts into :meth:`InferenceGeometry.scaled_int
 ``--pairs-per-launch N`` runs the scene through :meth:`UniMatch.forward_sequence` (``task='depth'``) instead: every frame is read,
 uploaded, prepared and encoded once, the absolute poses are uploaded once and the relative poses are formed on the device, N pairs go
 through the match step per launch, and the coloured images come back once per piece of N pairs.  The files written are those of the
-default mode; all frames must have one size.
+default mode; all frames must have one size.  ``--fuse-neighbours`` (with ``--pairs-per-launch``, not with ``--pred-bidir-depth``)
+lets the previous frame vote in every frame's plane sweep as a second source view: the Transformer has already produced its tokens, so
+it costs the sweep alone (``forward_sequence(fuse_neighbours=True)``; an unlearned fusion, the weights are trained on two views).
 
 Values and geometry (both modes write the same files):
 
@@ -125,17 +127,23 @@ class _SceneCollector:
 def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_size=None, min_depth=0.5, max_depth=10.,
               num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, scale_intrinsics=False, device='cuda',
               pairs_per_launch=None, save_depth=False, consistency_check=False, save_ply=None, ply_stride=1, min_views=1, px_thr=1.0,
-              rel_thr=0.01, save_confidence=False, min_confidence=None, peak_radius=1):
+              rel_thr=0.01, save_confidence=False, min_confidence=None, peak_radius=1, fuse_neighbours=False):
     """``inference_depth`` over the scene: returns the number of frames written (one less than the scene has).
     ``pairs_per_launch=N``: sequence mode (the module docstring), in pieces of N pairs; ``None``: one ``predict`` per pair.
     ``save_depth``, ``consistency_check``, ``save_ply`` (a file name): the value and geometry outputs of the module docstring.
     ``save_confidence``, ``min_confidence`` (with ``save_ply``), ``peak_radius``: the plane sweep's confidence, taken in the forward's
-    own matching launch (``forward_with_depth_confidence`` / ``forward_sequence(return_confidence=True)``)."""
+    own matching launch (``forward_with_depth_confidence`` / ``forward_sequence(return_confidence=True)``).
+    ``fuse_neighbours`` (sequence mode only, not with ``pred_bidir_depth``): the previous frame votes in every frame's plane sweep
+    (``forward_sequence(fuse_neighbours=True)``: an unlearned two-source fusion for the price of the sweep; the files are the same)."""
     from .confidence import confidence_to_image, confidence_to_image_size
     from .io import write_png8
     from .prepost import InferenceGeometry
     if min_confidence is not None and not save_ply:
         raise ValueError('min_confidence filters the point cloud: it needs save_ply')
+    if fuse_neighbours and pairs_per_launch is None:
+        raise ValueError('fuse_neighbours is an option of the sequence mode: it needs pairs_per_launch')
+    if fuse_neighbours and pred_bidir_depth:
+        raise ValueError('fuse_neighbours replaces the backward prediction: it cannot be combined with pred_bidir_depth')
     want_conf = bool(save_confidence) or min_confidence is not None
     imgs, poses, k = read_scene(scene_dir)
     os.makedirs(out_dir, exist_ok=True)
@@ -149,7 +157,8 @@ def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_si
     if pairs_per_launch is not None:
         return _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, inference_size, min_depth, max_depth,
                                    num_depth_candidates, depth_from_argmax, pred_bidir_depth, scale_intrinsics, device,
-                                   int(pairs_per_launch), collect, bool(save_confidence), want_conf, int(peak_radius))
+                                   int(pairs_per_launch), collect, bool(save_confidence), want_conf, int(peak_radius),
+                                   bool(fuse_neighbours))
     for i in range(len(imgs) - 1):
         ref, tgt = read_frame_u8(imgs[i])[None].to(device), read_frame_u8(imgs[i + 1])[None].to(device)
         size = tuple(inference_size) if inference_size else nearest_size(ref.shape[1:3], padding_factor)
@@ -190,7 +199,7 @@ def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_si
 
 def _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, inference_size, min_depth, max_depth,
                         num_depth_candidates, depth_from_argmax, pred_bidir_depth, scale_intrinsics, device, step, collect=None,
-                        save_confidence=False, want_conf=False, peak_radius=1):
+                        save_confidence=False, want_conf=False, peak_radius=1, fuse_neighbours=False):
     """The scene through ``forward_sequence(task='depth')`` in pieces of ``step`` pairs (``step + 1`` frames first, then ``step`` frames
     joined by the carry), so that at most ``step + 1`` frames and their predictions are resident."""
     from .confidence import confidence_to_image, confidence_to_image_size
@@ -201,6 +210,7 @@ def _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, 
     if len(imgs) < 2:
         return 0
     geom = intrinsics = carry = shape = pending = None
+    fuse_kw = {'fuse_neighbours': True} if fuse_neighbours else {}                           # the carry then joins the pieces' sweeps too
     pose_dev = torch.from_numpy(poses).to(device)                                            # absolute, uploaded once
     lo = 0
     while lo < len(imgs):
@@ -224,7 +234,7 @@ def _run_depth_sequence(model, imgs, poses, k, out_dir, fwd_kw, padding_factor, 
                                          pairs_per_launch=step, min_depth=1. / max_depth, max_depth=1. / min_depth,
                                          num_depth_candidates=num_depth_candidates, depth_from_argmax=depth_from_argmax,
                                          pred_bidir_depth=pred_bidir_depth, return_confidence=want_conf, peak_radius=peak_radius,
-                                         **fwd_kw)
+                                         **fuse_kw, **fwd_kw)
         carry = out['carry']
         first = lo - (0 if lo == 0 else 1)                                                   # the frame of the piece's first pair
         depth = [out['depth']] + ([out['depth_bwd']] if pred_bidir_depth else [])
@@ -275,6 +285,9 @@ def main(argv=None):
     ap.add_argument('--scale-intrinsics', action='store_true', help='rescale the intrinsics with the resize (the reference does not)')
     ap.add_argument('--pairs-per-launch', type=int, default=None, metavar='N',
                     help='sequence mode: encode every frame once and match N pairs per launch (frames of one size)')
+    ap.add_argument('--fuse-neighbours', action='store_true',
+                    help='with --pairs-per-launch: the previous frame votes in every plane sweep as a second view (unlearned fusion; '
+                         'not with --pred-bidir-depth)')
     ap.add_argument('--save-depth', action='store_true', help='write <stem>_depth.png: 16-bit millimetres')
     ap.add_argument('--consistency-check', action='store_true', help='write <stem>_occ.png: 255 where the neighbouring frames disagree')
     ap.add_argument('--save-ply', default=None, metavar='FILE', help='write the fused, filtered, coloured point cloud of the scene')
@@ -292,6 +305,10 @@ def main(argv=None):
                                                     'default: the seeded synthetic weights')
     ap.add_argument('--precision', default='exact', choices=['exact', 'fast'])
     args = ap.parse_args(argv)
+    if args.fuse_neighbours and args.pairs_per_launch is None:
+        ap.error('--fuse-neighbours needs --pairs-per-launch (it is an option of the sequence mode)')
+    if args.fuse_neighbours and args.pred_bidir_depth:
+        ap.error('--fuse-neighbours cannot be combined with --pred-bidir-depth (it replaces the backward prediction)')
     model, fwd_kw = load_model(args.model_config, args.weights, args.precision)
     n = run_depth(model, args.scene, args.out, fwd_kw, padding_factor=args.padding_factor, inference_size=args.inference_size,
                   min_depth=args.min_depth, max_depth=args.max_depth, num_depth_candidates=args.num_depth_candidates,
@@ -299,7 +316,7 @@ def main(argv=None):
                   scale_intrinsics=args.scale_intrinsics, pairs_per_launch=args.pairs_per_launch, save_depth=args.save_depth,
                   consistency_check=args.consistency_check, save_ply=args.save_ply, ply_stride=args.ply_stride, min_views=args.min_views,
                   px_thr=args.px_thr, rel_thr=args.rel_thr, save_confidence=args.save_confidence, min_confidence=args.min_confidence,
-                  peak_radius=args.peak_radius)
+                  peak_radius=args.peak_radius, fuse_neighbours=args.fuse_neighbours)
     print(f'{n} frames written to {args.out}')
 
 

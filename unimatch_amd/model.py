@@ -335,6 +335,22 @@ def _rigid_flow(depth, intrinsics, pose):
     return (proj[:, :2] / proj[:, 2:].clamp(min=1e-3)).view(b, 2, h, w) - grid
 
 
+def neighbour_rows(nb, carried):
+    """The row table ``[2, nb, 3]`` int32 (f0 row | f1 row | cam row) of a fused sequence chunk of ``nb`` consecutive pairs
+    (``um_depth_corr_softmax_multi_rows``).  Token rows index the segments ``tok0 [nb] | tok1 [nb] | the carried pair's tok0, tok1 [2]``;
+    cam rows index the bidirectional pack of ``n = nb + carried`` pairs, the carried pair first: forward cams ``[0, n)``, inverse cams
+    ``[n, 2n)``.  Source 0 "next" of frame t is ``(t, nb + t, carried + t)``; source 1 "previous" is pair t - 1 seen from its second
+    frame, ``(nb + t - 1, t - 1, n + carried + t - 1)`` -- the row that is f1 of one sample is f0 of the next.  Frame 0 takes the carried
+    pair ``(2 nb + 1, 2 nb, n)`` or, without one, is off (-1: the launch never reads an off source)."""
+    c = 1 if carried else 0
+    n = nb + c
+    t = torch.arange(nb, dtype=torch.int32)
+    nxt = torch.stack([t, nb + t, c + t], 1)
+    prv = torch.stack([nb + t - 1, t - 1, n + c + t - 1], 1)
+    prv[0] = torch.tensor([2 * nb + 1, 2 * nb, n] if c else [-1, -1, -1], dtype=torch.int32)
+    return torch.stack([nxt, prv], 0).contiguous()
+
+
 class UniMatch(nn.Module):
     def __init__(self, num_scales=1, feature_channels=128, upsample_factor=8, num_head=1, ffn_dim_expansion=4,
                  num_transformer_layers=6, reg_refine=False, task='flow'):
@@ -577,6 +593,49 @@ class UniMatch(nn.Module):
         from .confidence import depth_match_multi
         return depth_match_multi(f0, f1, h, w, cams, cand, use, from_argmax=from_argmax)[0]
 
+    def _neighbour_rows(self, nb, carried, device):
+        """:func:`neighbour_rows` on ``device``: a pure function of (pairs in the chunk, carry present), uploaded once per device and
+        cached as ``_position`` and ``_constants`` are, so a warm call copies nothing and never waits for the device."""
+        key = ('nbr_rows', int(nb), bool(carried), str(device))
+        if key not in self._pos_cache:
+            self._pos_cache[key] = neighbour_rows(int(nb), bool(carried)).to(device)
+        return self._pos_cache[key]
+
+    def _sweep_neighbours(self, ops, tok0, tok1, h, w, intrinsics, pose, up, cand, neighbour, from_argmax, confidence, peak_radius):
+        """The fused plane sweep of the ``nb`` consecutive pairs of a sequence chunk (``_match``'s ``neighbour``): ``(out [nb, 1, h, w],
+        cam [nb, 30] of the forward pairs)``.  ONE cam pack of the carried pair and the chunk's pairs in both directions, ONE
+        ``um_depth_corr_softmax_multi_rows`` launch on ``tok0``, ``tok1`` as the Transformer left them and the carried pair's two rows;
+        host tensors go through ``confidence.depth_match_multi``'s restatement.  Leaves the last pair in ``neighbour['out']``."""
+        from .confidence import depth_match_multi
+        nb = tok0.shape[0]
+        carried = neighbour['carry']
+        c = 0 if carried is None else 1
+        k_all, p_all = intrinsics, pose
+        if c:
+            k_all, p_all = torch.cat([carried['intrinsics'], intrinsics], 0), torch.cat([carried['pose'], pose], 0)
+        if hasattr(ops, 'depth_cam') and tok0.is_cuda:
+            cam_all = ops.depth_cam(k_all, p_all, float(up), True)
+        else:
+            kc = k_all.clone()
+            kc[:, :2] = kc[:, :2] / up
+            kc = kc.repeat(2, 1, 1)
+            pc = torch.cat([p_all, torch.inverse(p_all)], 0)
+            cam_all = torch.cat([torch.inverse(kc).flatten(1), pc[:, :3, :3].flatten(1), pc[:, :3, 3], kc.flatten(1)], 1).float().contiguous()
+        rows = self._neighbour_rows(nb, c, tok0.device)
+        tok0, tok1 = tok0.contiguous(), tok1.contiguous()              # they are: slices of the Transformer's output along dim 0
+        segments = [tok0, tok1] + ([carried['tokens']] if c else [])
+        if confidence is not None:
+            out, conf = depth_match_multi_confidence(ops if tok0.is_cuda else None, segments, None, h, w, cam_all, cand, None, from_argmax,
+                                                     up, peak_radius, rows=rows)
+            confidence.update(conf)
+        elif tok0.is_cuda:
+            out = ops.depth_corr_softmax(segments, None, h, w, cam_all, cand, from_argmax, rows=rows)
+        else:
+            out = depth_match_multi(segments, None, h, w, cam_all, cand, from_argmax=from_argmax, rows=rows)[0]
+        neighbour['out'] = {'tokens': torch.stack([tok0[nb - 1], tok1[nb - 1]], 0), 'pose': pose[nb - 1:].clone(),
+                            'intrinsics': intrinsics[nb - 1:].clone()}
+        return out, cam_all[c:c + nb]
+
     def forward_multiview(self, img_ref, img_srcs, *, intrinsics, poses, attn_type=None, attn_splits_list=None, prop_radius_list=None,
                           num_reg_refine=1, min_depth=1. / 0.5, max_depth=1. / 10, num_depth_candidates=64, depth_from_argmax=False,
                           pred_bidir_depth=False, task='depth', return_confidence=False, peak_radius=1):
@@ -791,7 +850,7 @@ class UniMatch(nn.Module):
                          num_reg_refine=1, pred_bidir_flow=False, consistency_check=False, colorize=False, pairs_per_launch=8,
                          carry=None, task='flow', intrinsics=None, poses=None, min_depth=1. / 0.5, max_depth=1. / 10,
                          num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, track_points=None,
-                         return_confidence=False, interpolate=0, peak_radius=1):
+                         return_confidence=False, interpolate=0, peak_radius=1, fuse_neighbours=False):
         """Optical flow of every pair (t, t+1) of a frame sequence ``frames [T, 3, H, W]`` (raw 0..255), each frame encoded ONCE.
 
         The reference's ``inference_flow`` (evaluate_flow.py:640-831) runs the model on each pair, so every interior frame goes through
@@ -836,7 +895,27 @@ class UniMatch(nn.Module):
         (``visualize.inverse_depth_to_image``).  With ``return_confidence`` the result gains ``'depth_confidence'``, what
         :meth:`forward_with_depth_confidence` returns (window ``peak_radius``), taken in the chunk's own plane-sweep launch: the maps
         ``[P, h, w]`` of the forward direction, ``scale`` and ``num_candidates``; a chunk then runs as one part.  On the GPU a depth call never waits for the device.  The depth keywords are ignored
-        for ``task='flow'``."""
+        for ``task='flow'``.
+
+        ``fuse_neighbours=True`` (depth only): the PREVIOUS frame votes in every frame's plane sweep as a second source view, for the
+        price of the sweep alone.  The Transformer is symmetric in its two halves, so pair t - 1 has already produced frame t's tokens
+        conditioned on frame t - 1 and frame t - 1's conditioned on frame t; with the inverse of that pair's relative pose (and that
+        pair's intrinsics row, as ``pred_bidir_depth`` uses it) they are a second source of reference frame t.  Frame t >= 1 fuses source
+        0 "next" ``(tok0[t], tok1[t], cam of pair t)`` and source 1 "previous" ``(tok1[t-1], tok0[t-1], inverse cam of pair t-1)`` in ONE
+        launch per chunk (``um_depth_corr_softmax_multi_rows``: the operands are rows of the Transformer's output, named by a cached
+        row table and not copied; the cam pack stays one launch per chunk); the logits are averaged over the sources that see a
+        candidate before the one softmax, as in :meth:`forward_multiview`, which computes the same thing per frame at twice the
+        Transformer work.  This is an UNLEARNED extension: the weights are trained on two views; the mean over the seeing sources
+        keeps the logits at the scale the softmax was trained at.  Propagation, upsampling and refinement run on source 0 exactly as
+        without the flag.  The keys and shapes of the result are unchanged (``'depth' [P, H, W]`` is the depth of frame t of pair t;
+        the last frame of a video keeps having no entry); with ``return_confidence`` the statistics are those of the FUSED
+        distribution, from the same launch.  A chunk runs as one part.  The carry gains ``'neighbour'``: the last pair's two token
+        rows after the Transformer (cloned), its relative pose and its intrinsics row, which the next chunk -- of this call or of
+        the next -- passes as a third segment, so a video fed in pieces that give the same chunk shapes gives the same bytes as one
+        call.  The first frame of a call without a usable carry has source 1 OFF (the two-view distribution); so has the first frame
+        after a stale carry (see above: its frame is encoded again) and after a carry made without the flag, which holds no
+        ``'neighbour'``.  Refused with ``task='flow'`` and with ``pred_bidir_depth`` (the backward prediction is what the fused sweep
+        replaces)."""
         if self.training:
             raise RuntimeError('this module implements inference only: call .eval()')
         if task == 'stereo':
@@ -856,10 +935,15 @@ class UniMatch(nn.Module):
             raise ValueError('interpolate needs pred_bidir_flow=True (the flows of both directions)')
         if return_confidence and task == 'flow' and -1 not in (corr_radius_list or ()):
             raise ValueError('return_confidence needs a global matching step (a corr_radius of -1 in corr_radius_list)')
+        if fuse_neighbours and task != 'depth':
+            raise ValueError("fuse_neighbours fuses the previous frame into the plane sweep: it needs task='depth'")
+        if fuse_neighbours and pred_bidir_depth:
+            raise ValueError('fuse_neighbours replaces the backward prediction: it cannot be combined with pred_bidir_depth')
         if task == 'depth':
             return self._depth_sequence(frames, attn_type, attn_splits_list, prop_radius_list, num_reg_refine, pred_bidir_flow,
                                         consistency_check, colorize, pairs_per_launch, carry, intrinsics, poses, min_depth, max_depth,
-                                        num_depth_candidates, depth_from_argmax, pred_bidir_depth, return_confidence, peak_radius)
+                                        num_depth_candidates, depth_from_argmax, pred_bidir_depth, return_confidence, peak_radius,
+                                        bool(fuse_neighbours))
         self._check_bidir_flow(pred_bidir_flow)
         if consistency_check and not pred_bidir_flow:
             raise AssertionError('consistency_check needs pred_bidir_flow=True (as the reference asserts)')
@@ -977,9 +1061,10 @@ class UniMatch(nn.Module):
 
     def _depth_sequence(self, frames, attn_type, attn_splits_list, prop_radius_list, num_reg_refine, pred_bidir_flow, consistency_check,
                         colorize, pairs_per_launch, carry, intrinsics, poses, min_depth, max_depth, num_depth_candidates,
-                        depth_from_argmax, pred_bidir_depth, return_confidence=False, peak_radius=1):
+                        depth_from_argmax, pred_bidir_depth, return_confidence=False, peak_radius=1, fuse_neighbours=False):
         """:meth:`forward_sequence` for ``task='depth'`` (documented there).  Frame j of the call -- the carried frame first, when
-        there is a carry -- has pose ``pose_all[j]`` and intrinsics ``k_all[j]``; pair j is frames (j, j + 1)."""
+        there is a carry -- has pose ``pose_all[j]`` and intrinsics ``k_all[j]``; pair j is frames (j, j + 1).  ``fuse_neighbours``:
+        ``nbr`` is the pair before the next chunk's first one as ``_match`` left it (tokens, relative pose, intrinsics row) or None."""
         # what forward (_forward_one) asserts for depth
         assert not pred_bidir_flow, 'pred_bidir_flow is a flow option'
         assert not consistency_check, 'consistency_check is a flow option (it needs pred_bidir_flow)'
@@ -1026,11 +1111,14 @@ class UniMatch(nn.Module):
             pose_all = poses.to(dev).float()
             k_all = intrinsics.to(dev).float().expand(count, 3, 3)
             prev = None
+            nbr = None
             if carry is not None:
                 pose_all = torch.cat([carry['pose'].to(dev), pose_all], 0)
                 k_all = torch.cat([carry['intrinsics'].to(dev), k_all], 0)
                 if self._carry_valid(carry, frames):
                     prev = carry['features']
+                    if fuse_neighbours:                   # None in a carry made without the flag: a first frame, source 1 off
+                        nbr = carry.get('neighbour')
                 else:                                     # stale: the stored frame is encoded with the first chunk
                     frames = torch.cat([carry['frame'].to(dev), frames], 0)
             if hasattr(ops, 'relative_pose_pairs') and pose_all.is_cuda:   # every pair of the call in one launch, no sync
@@ -1045,7 +1133,10 @@ class UniMatch(nn.Module):
                 nb = new.shape[0] - (1 if prev is None else 0)
                 i += new.shape[0]
                 conf = {} if return_confidence else None
-                pred = self._match_pairs(chunk, nb, kw, k_all[done:done + nb], rel[done:done + nb], confidence=conf)
+                neighbour = {'carry': nbr, 'out': None} if fuse_neighbours else None
+                pred = self._match_pairs(chunk, nb, kw, k_all[done:done + nb], rel[done:done + nb], confidence=conf, neighbour=neighbour)
+                if fuse_neighbours:
+                    nbr = neighbour['out']
                 if conf is not None:
                     confs.append({k: v[:nb] if torch.is_tensor(v) else v for k, v in conf.items()})
                 done += nb
@@ -1066,15 +1157,18 @@ class UniMatch(nn.Module):
                                               for k in confs[0]}
             result['carry'] = {'features': [p.clone() for p in prev], 'frame': last.clone(), 'state': self._carry_state(frames),
                                'pose': pose_all[-1:].clone(), 'intrinsics': k_all[-1:].clone()}
+            if fuse_neighbours:
+                result['carry']['neighbour'] = nbr
         return result
 
-    def _match_pairs(self, chunk, nb, kw, intrinsics=None, pose=None, confidence=None):
+    def _match_pairs(self, chunk, nb, kw, intrinsics=None, pose=None, confidence=None, neighbour=None):
         """The match step (task ``kw['task']``) of the ``nb`` pairs of consecutive frames whose features are ``chunk[s]`` (per scale, a
         list of pieces ``[N_i, C, h, w]`` that together hold the ``nb + 1`` frames in order) -> predictions ``[bidir * nb, ...]`` in the
         reference's [forward; backward] order.  The stream ``[F[lo:hi]; F[lo+1:hi+1]]`` of pairs lo .. hi-1 is ONE concatenation per
         scale.  ``intrinsics [nb, 3, 3]``, ``pose [nb, 4, 4]`` (depth): per pair, sliced with the features.  Where
         ``streams.forward_parts`` says so, the pairs run as concurrent parts on the process-wide side streams (``streams.PartRunner``);
-        with ``confidence`` (the dict ``_match`` fills) they run as one part."""
+        with ``confidence`` (the dict ``_match`` fills) or ``neighbour`` (``_match``: the previous pair as a second source of every
+        sweep, which ties each pair to the one before it) they run as one part."""
         def frames_of(pieces, a, b):                  # the pieces that hold frames a .. b-1 of the chunk
             out, base = [], 0
             for t in pieces:
@@ -1094,8 +1188,9 @@ class UniMatch(nn.Module):
         h8, w8 = ref.shape[-2:]
         parts = self._plan_parts(self.launch_parts, kw['task'], kw['attn_type'], nb, self.upsample_factor * h8, self.upsample_factor * w8,
                                  ref.is_cuda)
-        if parts <= 1 or confidence is not None:
-            return self._match(stream(0, nb), nb, intrinsics=intrinsics, pose=pose, confidence=confidence, **kw)['flow_preds'][0]
+        if parts <= 1 or confidence is not None or neighbour is not None:
+            more = {} if neighbour is None else {'neighbour': neighbour}
+            return self._match(stream(0, nb), nb, intrinsics=intrinsics, pose=pose, confidence=confidence, **more, **kw)['flow_preds'][0]
 
         def prepare(r):
             lo, hi = shard_bounds(nb, r, parts)
@@ -1181,7 +1276,7 @@ class UniMatch(nn.Module):
     def _match(self, feats, nb, attn_type='', attn_splits_list=None, corr_radius_list=None, prop_radius_list=None, num_reg_refine=1,
                pred_bidir_flow=False, task='flow', intrinsics=None, pose=None, min_depth=1. / 0.5, max_depth=1. / 10,
                num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, stream_has_pos=False, pred_out=None,
-               confidence=None, peak_radius=1, sources=0, use=None):
+               confidence=None, peak_radius=1, sources=0, use=None, neighbour=None):
         """The match step: everything after the encoder, on per-scale features ``feats[s] = [f0; f1]`` (``[2 nb, C, h, w]``, the
         first images of the ``nb`` pairs, then the second ones).  ``stream_has_pos``: the encoder added the position table already
         (``_forward_one`` decides; one scale, no refinement).  ``pred_out``: see ``_forward_one``.  ``confidence``: a dict that receives
@@ -1189,12 +1284,19 @@ class UniMatch(nn.Module):
         ``confidence.depth_match_confidence`` of the plane sweep (window ``peak_radius``), whose launch then also writes the prediction.
         ``sources`` >= 1 (depth, one scale): the ``nb = sources * B`` pairs are ``B`` reference frames with ``sources`` source views each,
         source-major (``intrinsics`` / ``pose`` likewise); the views vote in ONE plane sweep (``um_depth_corr_softmax_multi``; ``use
-        [sources, B]`` switches views off per sample) and everything after it runs on the primary pairs, the rows ``[:B]``."""
+        [sources, B]`` switches views off per sample) and everything after it runs on the primary pairs, the rows ``[:B]``.
+        ``neighbour`` (depth, one scale, the ``nb`` pairs are CONSECUTIVE: pair t is frames (t, t + 1)): a dict ``{'carry': the pair
+        before pair 0 or None, 'out': None}``.  Pair t - 1 is then a second source of every sweep -- ``(tok1[t-1], tok0[t-1], inverse
+        cam of pair t-1)`` next to ``(tok0[t], tok1[t], cam of pair t)`` -- in ONE ``um_depth_corr_softmax_multi_rows`` launch that reads
+        the Transformer's output in place through :meth:`_neighbour_rows`; everything after the sweep sees what it sees without it.
+        ``'out'`` receives the last pair (``'tokens' [2, h*w, C]`` = its tok0 | tok1 rows, cloned, ``'pose'``, ``'intrinsics'``)."""
         ops = self.ops
         dev = feats[0].device
         flow, pred = None, None
         if sources:
             assert task == 'depth' and self.num_scales == 1 and not pred_bidir_depth and nb % sources == 0
+        if neighbour is not None:
+            assert task == 'depth' and self.num_scales == 1 and not pred_bidir_depth and not sources
         for s in range(self.num_scales):
             m0, m1 = feats[s][:nb], feats[s][nb:]                         # [B, C, h, w]
             both = None
@@ -1242,7 +1344,10 @@ class UniMatch(nn.Module):
                 f0c, f1c = tok0, tok1
                 if pred_bidir_depth:
                     f0c, f1c = torch.cat([tok0, tok1], 0), torch.cat([tok1, tok0], 0)
-                if hasattr(ops, 'depth_cam') and tok0.is_cuda:     # K / up, K^-1, (inverse) pose packed on the device, no sync
+                if neighbour is not None:
+                    flow_pred, cam = self._sweep_neighbours(ops, tok0, tok1, h, w, intrinsics, pose, up, cand.contiguous(), neighbour,
+                                                            depth_from_argmax, confidence, peak_radius)
+                elif hasattr(ops, 'depth_cam') and tok0.is_cuda:   # K / up, K^-1, (inverse) pose packed on the device, no sync
                     cam = ops.depth_cam(intrinsics, pose, float(up), pred_bidir_depth)
                 else:
                     kc, pc = k_cur, pose
@@ -1251,7 +1356,9 @@ class UniMatch(nn.Module):
                         pc = torch.cat([pose, torch.inverse(pose)], 0)
                     cam = torch.cat([torch.inverse(kc).flatten(1), pc[:, :3, :3].flatten(1), pc[:, :3, 3],
                                      kc.flatten(1)], 1).float().contiguous()
-                if sources:
+                if neighbour is not None:
+                    pass                                           # swept above, with the cam pack
+                elif sources:
                     b = nb // sources
                     flow_pred = self._sweep_multiview(ops, tok0, tok1, h, w, cam, cand.contiguous(), sources, use, depth_from_argmax, up,
                                                       confidence, peak_radius)

@@ -1504,7 +1504,7 @@ class HipOps(WorkspaceRegistry):
         _abi.check(code, 'um_prop_local_attn')
         return out
 
-    def depth_corr_softmax(self, f0, f1, h, w, cam, candidates, from_argmax=False, stats=False, peak_radius=1, use=None):
+    def depth_corr_softmax(self, f0, f1, h, w, cam, candidates, from_argmax=False, stats=False, peak_radius=1, use=None, rows=None):
         """cam ``[B, 30]`` = K^-1 | R | t | K (row major), candidates ``[D]`` inverse depths -> ``out [B, 1, h, w]``.
 
         ``stats=True``: the same sweep as ONE ``um_depth_corr_softmax_stats`` launch (recorded as ``'depth_corr_softmax_stats'``) that
@@ -1517,7 +1517,17 @@ class HipOps(WorkspaceRegistry):
         :meth:`_depth_corr_softmax_multi`; its memory-contract cases are in tests/test_depth_multiview_gpu.py.  Why one method has two
         layouts chosen by the rank of ``f0`` instead of a public ``depth_corr_softmax_multi``: the public method list of this class is
         pinned by tests/test_memory_contract_gpu.py (every public method needs a case or a reason in that file's tables), so a new
-        launch of an existing operation comes in through the existing method, as ``stats=True`` did."""
+        launch of an existing operation comes in through the existing method, as ``stats=True`` did.
+
+        ``rows [S, B, 3]`` int32 on the device: the same fused sweep on operands that are ROWS of other tensors
+        (``um_depth_corr_softmax_multi_rows``, recorded as ``'depth_corr_softmax_multi_rows'``).  ``f0`` is then a tuple or list of 1 .. 4
+        token tensors ``[n_i, h*w, 128]`` (the segments a token row indexes, concatenated in order), ``f1`` is None and ``cam`` is
+        ``[Rc, 30]``: see :meth:`_depth_corr_softmax_multi_rows`; its memory-contract cases are in
+        tests/test_depth_fuse_neighbours_gpu.py."""
+        if rows is not None:
+            if f1 is not None or use is not None:
+                raise ValueError('rows names every operand: f1 must be None (f0 holds the segments) and use must be None (an off source has a negative row)')
+            return self._depth_corr_softmax_multi_rows(f0, h, w, cam, rows, candidates, from_argmax, stats, peak_radius)
         if f0.dim() == 4:
             return self._depth_corr_softmax_multi(f0, f1, h, w, cam, candidates, use, from_argmax, stats, peak_radius)
         if use is not None:
@@ -1575,4 +1585,44 @@ class HipOps(WorkspaceRegistry):
             _ptr(planes) if stats else None, _ptr(index) if stats else None, s, b, h, w, c,
             candidates.numel(), int(bool(from_argmax)), int(peak_radius), _stream()))
         _abi.check(code, 'um_depth_corr_softmax_multi')
+        return (out, planes, index) if stats else out
+
+    def _depth_corr_softmax_multi_rows(self, segments, h, w, cam, rows, candidates, from_argmax=False, stats=False, peak_radius=1):
+        """:meth:`depth_corr_softmax` with a row table (a private name, as :meth:`_depth_corr_softmax_multi`): the fused plane sweep of
+        ``S`` source views per sample whose operands are rows of the ``segments`` (1 .. 4 contiguous CUDA float32 tensors ``[n_i, h*w,
+        128]``; a token row indexes their concatenation in order) and of ``cam [Rc, 30]``.  ``rows [S, B, 3]`` int32 on the device =
+        f0 row | f1 row | cam row; a source with a negative or too-large index is off for that sample and is never read, so no table
+        can make the kernel read out of bounds.  Returns what :meth:`_depth_corr_softmax_multi` returns, bit for bit its result on the
+        same operands copied into the source-major layout.  ONE launch, recorded as ``'depth_corr_softmax_multi_rows'``; the host does
+        not look at ``rows``: no synchronisation."""
+        if torch.is_tensor(segments) or not 1 <= len(segments) <= 4:
+            raise ValueError('rows: f0 must be a tuple or list of 1 .. 4 token tensors (the segments)')
+        l = h * w
+        for i, t in enumerate(segments):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.is_contiguous() and t.shape[0] >= 1
+                    and tuple(t.shape[1:]) == (l, 128) and t.device == segments[0].device):
+                raise ValueError(f'segment {i}: expected a contiguous CUDA float32 [n >= 1, {l}, 128] tensor on {segments[0].device}, got '
+                                 f'{tuple(t.shape)} {t.dtype} {t.device} contiguous={t.is_contiguous()}')
+        dev = segments[0].device
+        if not (cam.is_cuda and cam.dtype == torch.float32 and cam.is_contiguous() and cam.dim() == 2 and cam.shape[0] >= 1
+                and cam.shape[1] == 30 and cam.device == dev):
+            raise ValueError('cam: expected contiguous CUDA float32 [Rc >= 1, 30]')
+        if not (rows.is_cuda and rows.dtype == torch.int32 and rows.is_contiguous() and rows.dim() == 3 and 1 <= rows.shape[0] <= 8
+                and rows.shape[1] >= 1 and rows.shape[2] == 3 and rows.device == dev):
+            raise ValueError('rows: expected contiguous CUDA int32 [S = 1 .. 8, B, 3] = f0 row | f1 row | cam row')
+        if not (candidates.is_cuda and candidates.dtype == torch.float32 and candidates.is_contiguous()
+                and candidates.dim() == 1):
+            raise ValueError('candidates: expected contiguous CUDA float32 [D]')
+        s, b = rows.shape[:2]
+        n = len(segments)
+        seg_ptr = (ctypes.c_void_p * n)(*[_ptr(t) for t in segments])
+        seg_rows = (ctypes.c_int * n)(*[t.shape[0] for t in segments])
+        out = torch.empty((b, 1, h, w), dtype=torch.float32, device=dev)
+        planes = torch.empty((b, 4, h, w), dtype=torch.float32, device=dev) if stats else None
+        index = torch.empty((b, 2, h, w), dtype=torch.int32, device=dev) if stats else None
+        code = self._launch('depth_corr_softmax_multi_rows', lambda: self.lib.um_depth_corr_softmax_multi_rows(
+            seg_ptr, seg_rows, n, _ptr(cam), cam.shape[0], _ptr(rows), _ptr(candidates), _ptr(out),
+            _ptr(planes) if stats else None, _ptr(index) if stats else None, s, b, h, w, 128,
+            candidates.numel(), int(bool(from_argmax)), int(peak_radius), _stream()))
+        _abi.check(code, 'um_depth_corr_softmax_multi_rows')
         return (out, planes, index) if stats else out
