@@ -1,7 +1,12 @@
 """Row tables for the tests of ``um_depth_corr_softmax_multi_rows`` (tests/test_depth_fuse_neighbours_cpu.py, _gpu.py): the
 source-major operands of tests/depth_multiview_util.py scattered, in shuffled order, into 1 .. 4 segments between decoy rows of NaN,
-with the table that names them.  Plain torch on host tensors; deterministic per (shapes, segments, seed)."""
+with the table that names them; and the table of segment edges of row 10 of tests/test_dispatch_boundaries_gpu.py (``scatter_edges``).
+Plain torch on host tensors; deterministic per (shapes, segments, seed)."""
+import functools
+
 import torch
+
+from tests import depth_multiview_util as mv
 
 BIG = 2 ** 30                  # a row index far past every table of these tests
 
@@ -29,6 +34,57 @@ def scatter(f0, f1, cam, segments, seed=0, decoys=3):
     segs = [tokens[lo:hi].contiguous() for lo, hi in zip(bounds[:-1], bounds[1:])]
     rows = torch.stack([p0, p1, pc], -1).to(torch.int32).contiguous()
     return segs, table.contiguous(), rows
+
+
+def scatter_edges(f0, f1, cam, seed=0, decoys=3):
+    """``(segs, cam_table, rows, use)``: four segments of sizes 1, n, 1, m whose FIRST and LAST rows are all operands that ``rows`` names
+    (rows 0 | 1, n | n + 1 | n + 2, total - 1 of the concatenation), ``decoys`` rows of NaN elsewhere.  Source 1 is off in the last
+    sample: its f0 row is ``total``, the first index past the end, and the entry before it (source 1, the sample before) has f0 row
+    ``total - 1``, the last valid one.  ``use [S, B]`` uint8 is the mask the contiguous launch needs for the same sweep.  The operands of
+    the off source are in no segment.  Needs ``2 (S B - 1) >= 6`` operand rows and ``B >= 2``."""
+    s, b, l, c = f0.shape
+    assert b >= 2 and s >= 2 and 2 * (s * b - 1) >= 6
+    g = torch.Generator().manual_seed(5151 + 17 * seed)
+    use = torch.ones(s, b, dtype=torch.uint8)
+    use[1, b - 1] = 0
+    on = [(i, j) for i in range(s) for j in range(b) if use[i, j]]
+    total = 2 * len(on) + decoys
+    n = (total - 2) // 2
+    sizes = [1, n, 1, total - 2 - n]
+    edges = [0, 1, n, n + 1, n + 2, total - 1]
+    assert len(set(edges)) == 6 and min(sizes) >= 1
+    # operand k of 2 len(on): f0 of on[k // 2] (even k) or its f1 (odd k); the f0 of (1, b - 2) takes the last row, five others the
+    # remaining edges, the rest any other row
+    last = 2 * on.index((1, b - 2))
+    order = [k for k in torch.randperm(2 * len(on), generator=g).tolist() if k != last]
+    inner = [r for r in torch.randperm(total, generator=g).tolist() if r not in edges]
+    place = {last: total - 1}
+    place.update(zip(order[:5], edges[:5]))
+    place.update(zip(order[5:], inner))
+    tokens = torch.full((total, l, c), float('nan'), dtype=f0.dtype)
+    n_cam = s * b + decoys
+    pc = torch.randperm(n_cam, generator=g)[:s * b].view(s, b)
+    table = torch.full((n_cam, 30), float('nan'), dtype=cam.dtype)
+    rows = torch.zeros(s, b, 3, dtype=torch.int32)
+    for k, (i, j) in enumerate(on):
+        tokens[place[2 * k]], tokens[place[2 * k + 1]] = f0[i, j], f1[i, j]
+        table[pc[i, j]] = cam[i, j]
+        rows[i, j] = torch.tensor([place[2 * k], place[2 * k + 1], int(pc[i, j])], dtype=torch.int32)
+    rows[1, b - 1] = torch.tensor([total, 0, int(pc[0, 0])], dtype=torch.int32)            # ONE bad index: the first row past the end
+    bounds = [0, 1, n + 1, n + 2, total]
+    segs = [tokens[lo:hi].contiguous() for lo, hi in zip(bounds[:-1], bounds[1:])]
+    assert [t.shape[0] for t in segs] == sizes
+    return segs, table.contiguous(), rows.contiguous(), use
+
+
+@functools.lru_cache(maxsize=None)
+def edges_case(case):
+    """``scatter_edges`` of a case of tests/depth_multiview_util.py with the float64 reference of the same sweep (source 1 off in the
+    last sample): ``(segs, cam_table, rows, use, reference)``, computed once, shared, never modified."""
+    (b, h, w), d, moves = mv.CASES[case]
+    f0, f1, cam, cand = mv.inputs(case)
+    segs, table, rows, use = scatter_edges(f0, f1, cam, seed=len(moves) + d)
+    return segs, table, rows, use, mv.reference_of(f0, f1, h, w, cam, cand, use)
 
 
 def switch_off(rows, use, total_rows, cam_rows, shift=0):

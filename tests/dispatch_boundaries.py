@@ -44,22 +44,22 @@ def attn_uses_token_table(win_h, win_w):
     return (win_h * win_w + 31) // 32 * 32 * 4 <= TAB_BYTES
 
 
-PIXEL_GRID_CAP = 256 * 16         # local_ops.hip:764: workgroups of 4 waves, one pixel per wave and trip
+PIXEL_GRID_CAP = 256 * 16         # local_pixel.h:107: workgroups of 4 waves, one pixel per wave and trip
 
 
 def pixel_grid_trips(pixels):
-    """local_ops.hip:762 (pixel_grid_blocks) and the ``pid += gridDim.x * 4`` loops behind it: trips of the busiest wave."""
+    """local_pixel.h:105 (pixel_grid_blocks) and the ``pid += gridDim.x * 4`` loops behind it: trips of the busiest wave."""
     blocks = min((pixels + 3) // 4, PIXEL_GRID_CAP)
     return (pixels + 4 * blocks - 1) // (4 * blocks)
 
 
 def depth_uses_box_kernel(candidates):
-    """local_ops.hip:912, 941 -- lane = candidate while the candidates fit one wave."""
+    """local_ops.hip:812, 841 and depth_multi.hip:679, 746 -- lane = candidate while the candidates fit one wave."""
     return candidates <= 64
 
 
-LOCAL_MAX_TAPS = 16 * 8           # local_ops.hip:22 (LOCAL_MAX_ROUNDS 8), checked at :773, :892, :906, :931
-K4_MAX_TAPS = 81                  # local_ops.hip:143, checked at :791, :874
+LOCAL_MAX_TAPS = 16 * 8           # local_pixel.h:7 (LOCAL_MAX_ROUNDS 8), checked at local_ops.hip:673, :792, :806, :831
+K4_MAX_TAPS = 81                  # local_ops.hip:100, checked at :691, :774
 
 
 def conv_tile_width(cout):

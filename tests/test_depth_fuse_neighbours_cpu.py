@@ -71,7 +71,7 @@ def _source_major(case, use=None, peak_radius=2):
     return logits, confidence.depth_match_multi(f0, f1, h, w, cam, cand, use, peak_radius=peak_radius)
 
 
-@pytest.mark.parametrize('segments', [1, 2, 3])
+@pytest.mark.parametrize('segments', [1, 2, 3, 4])
 @pytest.mark.parametrize('case', CASES)
 def test_rows_equal_the_source_major_call(case, segments):
     (b, h, w), d, moves = mv.CASES[case]

@@ -41,7 +41,7 @@ def same(got, want, label):
 
 # ------------------------------------------------------------------ 1. the rows launch is the contiguous launch, bit for bit
 @pytest.mark.parametrize('argmax', [False, True])
-@pytest.mark.parametrize('segments', [1, 2, 3])
+@pytest.mark.parametrize('segments', [1, 2, 3, 4])
 @pytest.mark.parametrize('case', CASES)
 def test_rows_launch_is_the_contiguous_launch(ops, case, segments, argmax):
     (b, h, w), d, moves = mv.CASES[case]

@@ -37,27 +37,7 @@ def dev(*tensors):
     return tuple(t.to(DEV) for t in tensors)
 
 
-def compare(got, ref, d, label):
-    """``got = (out, stats, index)`` of the device against a float64 reference dict, by the gates of the module docstring."""
-    out, stats, index = (t.cpu() for t in got)
-    assert index.dtype == torch.int32 and bool(torch.isfinite(stats).all()) and bool(torch.isfinite(out).all())
-    sc = mv.scales(d)
-    dist = {'out': (out.double() - ref['out']).abs().max().item()}
-    for i, name in enumerate(mv.FLOATS):
-        dist[name] = (stats[:, i].double() - getattr(ref['stats'], name)).abs().max().item()
-    print(f'{label}: ' + ' '.join(f'{k} {v:.2e}/{TOL * sc[k]:.2e}' for k, v in dist.items()))
-    for name, v in dist.items():
-        assert v <= TOL * sc[name], (label, name, v, TOL * sc[name])
-    best, seen = index[:, 0].long(), index[:, 1]
-    assert bool((best >= 0).all()) and bool((best < d).all())
-    picked = ref['prob'].gather(1, best[:, None])[:, 0]
-    assert (ref['prob'].amax(1) - picked).max().item() <= TOL                      # value optimality: no row excluded
-    wide = ref['gap'] >= 0.1
-    assert torch.equal(best[wide], ref['prob'].argmax(1)[wide])
-    clear = ref['clear']
-    assert clear.float().mean().item() >= 0.90, clear.float().mean().item()
-    assert torch.equal(seen[clear], ref['stats'].in_view[clear])
-    assert bool((seen >= 0).all()) and bool((seen <= d).all())
+compare = mv.compare              # the gates of the module docstring; rows 8 .. 11 of tests/test_dispatch_boundaries_gpu.py share them
 
 
 # ------------------------------------------------------------------ 1. against float64

@@ -1,14 +1,17 @@
 """The host side of the kernel-selection rules, without a GPU: the exported plan / split / part-count functions on both sides of every
 switch, the Python restatements tests/dispatch_boundaries.py uses against the library's answers, the refusals one step beyond the
-advertised tap and candidate range (decided on the host before any HIP call), and the conditioning of the arg-max read-out's inputs.
+advertised tap and candidate range (decided on the host before any HIP call), the conditioning of the arg-max read-out's inputs, and
+(at the end) the properties of the multi-view sweeps' inputs of rows 8 .. 11 with three seeded defects that their gate rejects.
 Without a device the library's CU count is its fallback of 256 (common.h:19-28); every assertion below holds for any count."""
 import ctypes
 
 import pytest
 import torch
 
+from tests import depth_fuse_neighbours_util as fu
+from tests import depth_multiview_util as mv
 from tests import dispatch_boundaries as db
-from unimatch_amd import _abi
+from unimatch_amd import _abi, confidence
 
 
 @pytest.fixture(scope='module')
@@ -92,7 +95,7 @@ def test_ffn_split_slice_conditions(lib):
 
 # ------------------------------------------------------------------ local family: grid cap, tap range, refusals
 def test_pixel_grid_cap_is_16384_pixels():
-    """local_ops.hip:762-767."""
+    """local_pixel.h:105-110."""
     assert db.pixel_grid_trips(128 * 128) == 1 and db.pixel_grid_trips(129 * 128) == 2 and db.pixel_grid_trips(1) == 1
     assert db.pixel_grid_trips((2 * 363 * 362 + 15) // 16) == 2 and db.pixel_grid_trips(262144 // 16) == 1   # K4: blocks of 16 pixels
 
@@ -108,8 +111,8 @@ def _buffers():
 
 
 def test_refusals_beyond_the_tap_range_are_decided_on_the_host(lib):
-    """One step beyond LOCAL_MAX_ROUNDS x 16 = 128 taps / candidates (local_ops.hip:773, 892, 906, 931) and beyond the cost volume's 81
-    taps (:791, :874): UM_ERR_UNSUPPORTED and a message, on 8 x 8 maps."""
+    """One step beyond LOCAL_MAX_ROUNDS x 16 = 128 taps / candidates (local_ops.hip:673, 792, 806, 831) and beyond the cost volume's 81
+    taps (:691, :774): UM_ERR_UNSUPPORTED and a message, on 8 x 8 maps."""
     keep, (a, b, c, d, e, f, g) = _buffers()
     lib.um_census_enable(1)
     calls = {
@@ -214,3 +217,219 @@ def test_convolution_refuses_two_output_channels_on_the_host(lib):
 def test_norm_statistics_parts_of_the_gpu_rows():
     """nhwc_ops.hip:15, 74-75: chunks of 256 pixels; up to 1024 parts stay in registers."""
     assert 512 * 512 // db.NORM_CHUNK_ROWS == db.NORM_PARTS_IN_REGISTERS and 513 * 512 // db.NORM_CHUNK_ROWS == db.NORM_PARTS_IN_REGISTERS + 2
+
+
+# ------------------------------------------------------------------ rows 8 .. 11: the multi-view plane sweeps, on the reference alone
+# What the inputs of rows 8 .. 11 of the GPU file must be for those rows to be able to fail, asserted on the float64 reference; the
+# host twin of the segment-edge table; and three seeded defects that mv.compare rejects at the row that targets each.
+def test_multi_view_cap_geometries_sit_where_they_are_meant_to():
+    """local_pixel.h:105-110: 16384 pixels are the last one-trip map; 129 x 128 sends 32 workgroups round again; at 2 x 91 x 91 sample 1
+    starts inside a workgroup and 178 pixels are on the second trip."""
+    assert db.PIXEL_GRID_CAP * 4 == mv.GRID_PIXELS == 16384
+    assert [db.pixel_grid_trips(b * h * w) for b, h, w in ((1, 128, 128), (1, 129, 128), (2, 91, 91))] == [1, 2, 2]
+    assert int(mv.second_trip(1, 128, 128).sum()) == 0 and int(mv.second_trip(1, 129, 128).sum()) == 128 == 32 * 4
+    trip = mv.second_trip(2, 91, 91)
+    assert int(trip.sum()) == 178 and not bool(trip[0].any()) and 91 * 91 == 8281 and 8281 % 4 != 0
+    assert {mv.BOUNDARY[n][1] for n in mv.BOUNDARY if n.startswith('cap-')} == {16, 65}
+    assert db.depth_uses_box_kernel(16) and not db.depth_uses_box_kernel(65)
+
+
+@pytest.mark.parametrize('name', [n for n in mv.BOUNDARY if n.startswith('cap-')])
+def test_multi_view_cap_inputs_cannot_go_soft(name):
+    """Row 8.  On the whole map: ``clear`` covers at least 0.90 and the largest |logit| exceeds 9 (the softmax is not flat).  On the
+    second trip (``pid >= 16384``): by mv.box_positions at least one source takes the box form and at least one the gather form, at
+    least 5 % of the (pixel, candidate) pairs have n_j = 1 and at least 15 % have n_j >= 2 -- a table, a `gathered` flag or a count
+    carried over from the first trip changes the result."""
+    (b, h, w), d, moves = mv.BOUNDARY[name]
+    ref = mv.boundary_reference(name)
+    clear, peak = ref['clear'].float().mean().item(), ref['logits'].abs().max().item()
+    print(f'{name}: clear {clear:.4f} |logit|max {peak:.2f}')
+    assert clear >= 0.90 and peak > 9, (name, clear, peak)
+    masked = mv.boundary_reference(name, True)
+    assert masked['clear'].float().mean().item() >= 0.90
+    assert (masked['out'][b - 1] - ref['out'][b - 1]).abs().max().item() > 2e-3          # the source that is off had a say
+    trip = mv.second_trip(b, h, w)
+    if not bool(trip.any()):
+        return
+    box = {m: (mv.box_positions(h, w, mv.camera(b, h, w, m), mv.candidates(d))[trip] <= mv.DEPTH_BOX).double().mean().item() for m in moves}
+    views = ref['views'].permute(0, 2, 3, 1)[trip]
+    share = [(views == n).double().mean().item() for n in range(len(moves) + 1)]
+    print(f'{name}: second trip, box form ' + ' '.join(f'{m} {v:.3f}' for m, v in box.items()) + ' | n_j = 0 | 1 | 2 | 3: '
+          + ' | '.join(f'{v:.3f}' for v in share))
+    assert any(v > 0 for v in box.values()) and any(v < 1 for v in box.values()), box
+    assert share[1] >= 0.05 and sum(share[2:]) >= 0.15, share
+
+
+@pytest.mark.parametrize('name', [n for n in mv.BOUNDARY if n.startswith(('s8-', 's5-'))])
+def test_multi_view_source_count_inputs(name):
+    """Row 9.  Eight sources: n_j takes each of the values 4, 5, 6 and 7 on at least 1 % of the (pixel, candidate) pairs and never less
+    than 4; five sources: 2, 3 and 4.  Under the mask the three samples keep 1, 4 and 7 (of five: 5) sources, each sample's result
+    differs from the unmasked sweep's, and ``clear`` covers at least 0.90 both times."""
+    (b, h, w), d, moves = mv.BOUNDARY[name]
+    s = len(moves)
+    ref = mv.boundary_reference(name)
+    share = [(ref['views'] == n).double().mean().item() for n in range(s + 1)]
+    print(f'{name}: n_j = 0 .. {s}: ' + ' | '.join(f'{v:.3f}' for v in share) + f' clear {ref["clear"].float().mean().item():.4f}')
+    top = s - 1                                                  # 'away' sees nothing
+    assert all(v >= 0.01 for v in share[top - (3 if s == 8 else 2):top + 1]) and share[s] == 0, share
+    assert sum(share[:top - (3 if s == 8 else 2)]) == 0, share
+    assert ref['clear'].float().mean().item() >= 0.90 and ref['logits'].abs().max().item() > 9
+    (mb, _, _), _, _, use = mv.boundary_geometry(name, True)
+    assert mb == 3 and use.sum(0).tolist() == [1, 4, min(7, s)]
+    masked = mv.boundary_reference(name, True)
+    assert masked['clear'].float().mean().item() >= 0.90
+    assert [int(masked['views'][i].max()) for i in range(3)] == [1, 4 - int(use[4, 1]), min(7, s) - int(use[4, 2])]
+    whole = mv.reference_of(*mv.boundary_inputs(name, True)[:2], h, w, *mv.boundary_inputs(name, True)[2:4])
+    for i in range(3 if s == 8 else 2):
+        assert (masked['out'][i] - whole['out'][i]).abs().max().item() > 2e-3, i
+
+
+@pytest.mark.parametrize('name', [n for n in mv.BOUNDARY if n.startswith('rounds-')])
+def test_multi_view_upper_round_inputs(name):
+    """Row 11.  Among the candidates of rounds 5 .. 7 of the gather form (index 80 and beyond) at least 15 % of the (pixel, candidate)
+    pairs are seen by two or more sources and at least two different counts n_j >= 1 occur on 5 % each: a count that goes wrong there does
+    not cancel.  ``clear`` covers at least 0.90."""
+    (b, h, w), d, moves = mv.BOUNDARY[name]
+    ref = mv.boundary_reference(name)
+    upper = ref['views'][:, 80:]
+    share = [(upper == n).double().mean().item() for n in range(len(moves) + 1)]
+    print(f'{name}: candidates 80 .. {d - 1}: n_j = 0 | 1 | 2 | 3: ' + ' | '.join(f'{v:.3f}' for v in share)
+          + f' clear {ref["clear"].float().mean().item():.4f}')
+    assert d > 80 and (d + 15) // 16 >= 6
+    assert sum(share[2:]) >= 0.15 and sum(v >= 0.05 for v in share[1:]) >= 2, share
+    assert ref['clear'].float().mean().item() >= 0.90 and ref['logits'].abs().max().item() > 9
+
+
+def test_nine_sources_are_refused_on_the_host_by_both_entry_points(lib):
+    """depth_multi.hip:665, :710 -- ``sources`` 1 .. 8; 0 and 9 are UM_ERR_UNSUPPORTED from um_depth_corr_softmax_multi and from
+    um_depth_corr_softmax_multi_rows, decided before any HIP call."""
+    keep, (a, b, c, d, e, f, g) = _buffers()
+    ptrs, counts = (ctypes.c_void_p * 1)(a), (ctypes.c_int * 1)(64)
+    for sources in (0, 9):
+        rc = lib.um_depth_corr_softmax_multi(a, b, c, None, d, e, f, g, sources, 1, 8, 8, 128, 16, 0, 1, None)
+        assert rc == db.UM_ERR_UNSUPPORTED and f'sources={sources}'.encode() in lib.um_last_error_string(), (sources, rc)
+        rc = lib.um_depth_corr_softmax_multi_rows(ptrs, counts, 1, c, 8, b, d, e, f, g, sources, 1, 8, 8, 128, 16, 0, 1, None)
+        assert rc == db.UM_ERR_UNSUPPORTED and f'sources={sources}'.encode() in lib.um_last_error_string(), (sources, rc)
+    del keep
+
+
+@pytest.mark.parametrize('case', ['B', 'C'])
+def test_segment_edge_table_names_what_it_was_made_from(case):
+    """Row 10, host twin.  fu.scatter_edges: segments of 1, n, 1, m rows; the first and the last row of every segment are named by an
+    entry that is on; ``total - 1`` and ``total`` are the f0 rows of neighbouring entries; depth_rows_to_source_major_host gives back
+    the operands the table was made from and switches the entry with row ``total`` off."""
+    (b, h, w), d, moves = mv.CASES[case]
+    f0, f1, cam, cand = mv.inputs(case)
+    segs, table, rows, use, ref = fu.edges_case(case)
+    sizes = [t.shape[0] for t in segs]
+    total = sum(sizes)
+    assert len(segs) == 4 and sizes[0] == sizes[2] == 1 and sizes[1] >= 2 and sizes[3] >= 2
+    first = [0, sizes[0], sizes[0] + sizes[1], total - sizes[3]]
+    edges = set(first) | {f + n - 1 for f, n in zip(first, sizes)}
+    named = set(rows[..., :2][use.bool()].flatten().tolist())
+    assert len(edges) == 6 and edges <= named and len(named) == 2 * int(use.sum())             # no row is named twice
+    flat = rows.view(-1, 3)
+    k = flat[:, 0].tolist().index(total - 1)
+    assert flat[k + 1, 0] == total and use.flatten().tolist()[k:k + 2] == [1, 0] and int((use == 0).sum()) == 1
+    tokens = torch.cat(segs, 0)
+    assert bool(torch.isnan(tokens).any()) and not bool(torch.isnan(tokens[sorted(named)]).any())
+    g0, g1, gc, on = confidence.depth_rows_to_source_major_host(segs, table, rows)
+    assert torch.equal(on, use.bool())
+    assert torch.equal(g0[on], f0[on]) and torch.equal(g1[on], f1[on]) and torch.equal(gc[on], cam[on])
+    logits, seen, views = confidence.depth_match_logits_multi_host([t.double() for t in segs], None, h, w, table.double(), cand.double(),
+                                                                   rows=rows)
+    assert torch.equal(logits, ref['logits']) and torch.equal(views, ref['views'])
+    assert ref['clear'].float().mean().item() >= 0.90
+
+
+def rejected(got, ref, d, label, gate=mv.compare_about_best):
+    """Whether the gate of rows 8 .. 11 of the GPU file rejects ``got``."""
+    try:
+        gate(got, ref, d, label)
+    except AssertionError:
+        return True
+    return False
+
+
+def test_a_tie_of_the_top_two_logits_moves_peak_mass_and_nothing_else():
+    """Why rows 8 .. 11 gate through mv.compare_about_best.  At 1 x 128 x 128 with D = 65 one pixel's top two float64 logits are less
+    than 1e-5 apart (4.3e-6), closer than fp32 resolves at |logit| ~ 10.  A result that is the float64 one except that this pixel's
+    ``best`` is the other candidate, with ``peak_mass`` about it, is as right as fp32 can be: mv.compare rejects it on ``peak_mass`` alone
+    (the two windows differ by 1.8e-3, nine times the gate), mv.compare_about_best accepts it -- and rejects the same result when its
+    ``peak_mass`` stays about the float64 ``best``, or when ``best`` moves at a pixel whose gap is not a tie."""
+    name = 'cap-1x128x128-d65'
+    (b, h, w), d, moves = mv.BOUNDARY[name]
+    ref = mv.boundary_reference(name)
+    gap = ref['gap']
+    assert gap.min().item() < 1e-5 < mv.FLIP_GAP
+    at = (gap == gap.min()).nonzero()[0]
+    i, y, x = (int(v) for v in at)
+    first, second = (int(v) for v in ref['prob'][i, :, y, x].topk(2)[1])
+    about = ref['prob'][i, max(0, second - 1):second + 2, y, x].sum().item()
+    moved = abs(about - ref['stats'].peak_mass[i, y, x].item())
+    print(f'{name}: pixel ({y}, {x}) gap {gap.min().item():.2e}, best {first} | {second}, peak_mass windows differ by {moved:.3e}')
+    assert moved > 5 * mv.TOL
+    good = mv.result_of(ref)
+    tied = tuple(t.clone() for t in good)
+    tied[2][i, 0, y, x] = second
+    assert rejected(tied, ref, d, 'tie, peak_mass about the float64 best')                      # best moved, peak_mass did not
+    tied[1][i, 3, y, x] = about
+    assert rejected(tied, ref, d, 'tie, plain compare', gate=mv.compare) and not rejected(tied, ref, d, 'tie, about its own best')
+    wide = (gap > 1.0).nonzero()[0]
+    i, y, x = (int(v) for v in wide)
+    other = tuple(t.clone() for t in good)
+    other[2][i, 0, y, x] = int(ref['prob'][i, :, y, x].topk(2)[1][1])
+    assert rejected(other, ref, d, 'best moved where the gap is wide')
+
+
+def test_compare_rejects_second_trip_pixels_under_the_first_samples_camera():
+    """Defect (i), row 8 at 2 x 91 x 91: the pixels with ``pid >= 16384`` (all in sample 1) are computed under sample 0's camera
+    ('forward' turns sample 1's view by 0.04 rad).  mv.compare accepts the float64 result itself and rejects the result with the defect
+    on those 178 pixels alone."""
+    for name in ('cap-2x91x91-d16', 'cap-2x91x91-d65'):
+        (b, h, w), d, moves = mv.BOUNDARY[name]
+        f0, f1, cam, cand, _ = mv.boundary_inputs(name)
+        ref = mv.boundary_reference(name)
+        good = mv.result_of(ref)
+        assert not rejected(good, ref, d, f'{name} unmodified')
+        assert not torch.equal(cam[:, 1], cam[:, 0])
+        wrong = mv.result_of(mv.reference_of(f0[:, 1:], f1[:, 1:], h, w, cam[:, :1], cand))
+        trip = mv.second_trip(b, h, w)
+        bad = tuple(t.clone() for t in good)
+        for t, e in zip(bad, wrong):
+            t[1][:, trip[1]] = e[0][:, trip[1]]
+        assert all(torch.equal(t[0], g[0]) and torch.equal(t[1][:, ~trip[1]], g[1][:, ~trip[1]]) for t, g in zip(bad, good))
+        assert rejected(bad, ref, d, f'{name} second trip under the camera of sample 0')
+
+
+def test_compare_rejects_a_source_count_clamped_at_three():
+    """Defect (ii), row 9: ``sum_s v_sj l_sj`` divided by ``min(n_j, 3)`` -- what S <= 3 cannot tell from the rule."""
+    for name in [n for n in mv.BOUNDARY if n.startswith(('s8-', 's5-'))]:
+        (b, h, w), d, moves = mv.BOUNDARY[name]
+        ref = mv.boundary_reference(name)
+        assert not rejected(mv.result_of(ref), ref, d, f'{name} unmodified')
+        total = ref['logits'] * ref['views'].clamp(min=1).double()
+        cand = mv.candidates(d)
+        bad = dict(ref, **mv.from_logits(total / ref['views'].clamp(1, 3).double(), cand, ref['stats'].in_view))
+        assert rejected(mv.result_of(bad), ref, d, f'{name} n_j clamped at 3')
+        # the same defect passes where no count exceeds 3: the cases the suite had
+        small = mv.reference('B')
+        kept = dict(small, **mv.from_logits(small['logits'] * small['views'].clamp(min=1).double() / small['views'].clamp(1, 3).double(),
+                                            mv.candidates(mv.CASES['B'][1]), small['stats'].in_view))
+        assert not rejected(mv.result_of(kept), small, mv.CASES['B'][1], 'case B n_j clamped at 3')
+
+
+@pytest.mark.parametrize('case', ['B', 'C'])
+def test_compare_rejects_a_row_of_segment_three_read_from_segment_two(case):
+    """Defect (iii), row 10: the first row of segment 3 resolves to the same offset of segment 2 (a ``ptr3`` / ``first3`` that is never
+    taken).  Segment 2's row is another operand, so the result is finite and plausible."""
+    (b, h, w), d, moves = mv.CASES[case]
+    cand = mv.candidates(d)
+    segs, table, rows, use, ref = fu.edges_case(case)
+    assert not rejected(mv.result_of(ref), ref, d, f'case {case} unmodified')
+    swapped = [t.clone() for t in segs]
+    swapped[3][0] = segs[2][0]
+    assert bool(torch.isfinite(segs[2][0]).all()) and not torch.equal(segs[3][0], segs[2][0])
+    g0, g1, gc, on = confidence.depth_rows_to_source_major_host(swapped, table, rows)
+    bad = mv.reference_of(g0, g1, h, w, gc, cand, on)
+    assert rejected(mv.result_of(bad), ref, d, f'case {case}: segment 3 row 0 read from segment 2')

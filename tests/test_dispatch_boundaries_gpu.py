@@ -20,6 +20,8 @@ import torch
 
 from oracle import hotpath as hp
 from tests import bf16_emulation as em
+from tests import depth_fuse_neighbours_util as fu
+from tests import depth_multiview_util as mv
 from tests import dispatch_boundaries as db
 from tests.dispatch_boundaries import C, err, record, rnd, tok
 from unimatch_amd import _abi, confidence
@@ -354,9 +356,9 @@ def test_ffn_kv_without_workspace_takes_the_fused_kernel(ops, lib, cus, hidden):
 
 
 # ================================================================== row 4: the per-pixel local kernels past their grid cap
-# local_ops.hip:762 -- pixel_grid_blocks caps the grid at 4096 workgroups of 4 waves; past 16384 pixels a wave takes a second trip of
-# pid += gridDim.x * 4 (local_corr_softmax_kernel :81, prop_local_attn_kernel, depth_corr_softmax{,_box}{,_stats}_kernel,
-# local_corr_with_flow_dilated_kernel :833).
+# local_pixel.h:105 -- pixel_grid_blocks caps the grid at 4096 workgroups of 4 waves; past 16384 pixels a wave takes a second trip of
+# pid += gridDim.x * 4 (local_ops.hip: local_corr_softmax_kernel :38, prop_local_attn_kernel :294, depth_corr_softmax{,_box}{,_stats}_kernel
+# :477, :539, local_corr_with_flow_dilated_kernel :733).  The multi-view sweeps past the same cap: row 8.
 CAP_SIZES = [(128, 128), (129, 128)]              # 16384 pixels: the last one-trip map | 16512: 32 workgroups go round again
 
 
@@ -423,7 +425,7 @@ def sweep_device(ops, b, h, w, nd, argmax=False, stats=False):
 @pytest.mark.parametrize('nd', [16, 65])
 def test_grid_cap_plane_sweep(ops, cus, hw, nd):
     """um_depth_corr_softmax and um_depth_corr_softmax_stats on the box kernel (16 candidates) and the gather kernel (65; the rule is
-    local_ops.hip:912, 941: ``num_candidates <= 64``).  The statistics against the float64 host restatement under the gates of
+    local_ops.hip:812, 841: ``num_candidates <= 64``).  The statistics against the float64 host restatement under the gates of
     tests/test_depth_stats_gpu.py: 2e-4 x the scale of each plane."""
     h, w = hw
     kernel = 'box' if db.depth_uses_box_kernel(nd) else 'gather'
@@ -481,7 +483,7 @@ def test_grid_cap_dilated_cost_volume(ops, lib, cus, hw):
 
 
 def test_grid_cap_cost_volume_at_dilation_one(ops, lib, cus):
-    """um_local_corr_with_flow walks 16 pixels per wave, so its cap (local_ops.hip:795-798) sits at 4096 x 4 x 16 = 262144 pixels:
+    """um_local_corr_with_flow walks 16 pixels per wave, so its cap (local_ops.hip:695-698) sits at 4096 x 4 x 16 = 262144 pixels:
     2 x 363 x 362 = 262812 pixels send 42 waves round again, and the second sample starts in mid-block.  134 MB per feature map; the
     fp64 oracle takes 3 s.  Radius 1: the matrix-core kernel serves radius 4 only.  (The one-trip side is every other cost-volume test.)"""
     b, h, w = 2, 363, 362
@@ -500,7 +502,7 @@ def test_grid_cap_cost_volume_at_dilation_one(ops, lib, cus):
 
 
 # ================================================================== row 5: the upper half of the tap and candidate range
-# LOCAL_MAX_ROUNDS 8 (local_ops.hip:22): up to 128 taps or candidates, refused beyond (:773, :892, :906, :931).
+# LOCAL_MAX_ROUNDS 8 (local_pixel.h:7): up to 128 taps or candidates, refused beyond (local_ops.hip:673, :792, :806, :831).
 @pytest.mark.parametrize('b,h,w', [(2, 13, 19), (1, 3, 4)])                 # 494 pixels | a map smaller than every window below
 def test_tap_range_local_corr_softmax(ops, lib, cus, b, h, w):
     """2-D radius 5 (121 taps: 8 rounds, 7 idle slots) and 1-D radius 41 and 63 (83 and 127 taps)."""
@@ -739,3 +741,158 @@ def test_norm_merge_at_1024_parts(ops, cus, hw):
     record('7 norm merge', f'{b}x{c}x{h}x{w}', f'{parts} parts ' + ('in registers' if parts <= db.NORM_PARTS_IN_REGISTERS else 'read twice'),
            'nhwc_stats_finalize_kernel', mx, 2e-5, cus)
     assert mx < 2e-5
+
+
+# ================================================================== rows 8 .. 11: the multi-view plane sweeps (csrc/depth_multi.hip)
+# um_depth_corr_softmax_multi and um_depth_corr_softmax_multi_rows pick depth_multi{,_rows}_box_kernel | _gather_kernel by
+# ``num_candidates <= 64`` (depth_multi.hip:679, :746) and size their grid with pixel_grid_blocks (local_pixel.h:105).  No census id
+# exists for them: the kernel of a record line is what that rule gives for the row's D.  Reference, inputs and gates are those of
+# tests/test_depth_multiview_gpu.py (mv.reference_of in float64 on the float32 inputs, mv.compare through mv.compare_about_best); every record line names the float
+# plane that came nearest its gate.  The properties of the inputs that make these cases able to fail, and three seeded defects that
+# mv.compare rejects, are in tests/test_dispatch_boundaries_cpu.py.
+def multi_kernel(d, launch):
+    return ('depth_multi_rows_' if launch == 'rows' else 'depth_multi_') + ('box' if db.depth_uses_box_kernel(d) else 'gather') + '_kernel'
+
+
+def check_multi(row, label, side, got, ref, d, cand, argmax, launch, cus):
+    """One launch's ``(out, stats, index)`` through mv.compare_about_best (mv.compare, with the float64 ``peak_mass`` taken about the
+    launch's own ``best``: on maps of this size the top two logits of a pixel can tie within fp32 rounding); with ``argmax`` the read-out
+    must be the candidate at ``best``, which mv.compare then gates (the rule of test_against_float64)."""
+    if argmax:
+        assert torch.equal(got[0][:, 0], cand[got[2][:, 0].long()])
+        ref = dict(ref, out=got[0].cpu().double())
+    dist = mv.compare_about_best(got, ref, d, f'{label} {launch}')
+    sc = mv.scales(d)
+    plane = max(dist, key=lambda k: dist[k] / sc[k])
+    record(row, f'{label}, {launch} launch, {plane}', side, multi_kernel(d, launch), dist[plane], mv.TOL * sc[plane], cus)
+
+
+def run_multi_case(ops, cus, row, name, variant, side):
+    """A BOUNDARY case of tests/depth_multiview_util.py on both launches: the contiguous one and the rows launch on the same operands
+    scattered into four segments (``variant`` 'use': the mask of mv.boundary_geometry on the contiguous launch, one bad row index per off
+    source on the rows launch).  The two agree bit for bit and each passes mv.compare against float64 on its own."""
+    masked, argmax = variant == 'use', variant == 'argmax'
+    (b, h, w), d, moves, use = mv.boundary_geometry(name, masked)
+    f0, f1, cam, cand, use = mv.boundary_inputs(name, masked)
+    ref = mv.boundary_reference(name, masked)
+    segs, table, rows = fu.scatter(f0, f1, cam, 4, seed=len(name))
+    if masked:
+        bad = fu.switch_off(rows, use, sum(t.shape[0] for t in segs), table.shape[0], shift=len(moves))
+        assert int((bad != rows).any(-1).sum()) == int((use == 0).sum()) > 0
+        rows = bad
+    cand_d = cand.to(DEV)
+    whole = ops.depth_corr_softmax(f0.to(DEV), f1.to(DEV), h, w, cam.to(DEV), cand_d, argmax, stats=True,
+                                   use=use.to(DEV) if masked else None)
+    by_rows = ops.depth_corr_softmax([t.to(DEV) for t in segs], None, h, w, table.to(DEV), cand_d, argmax, stats=True, rows=rows.to(DEV))
+    assert tuple(whole[0].shape) == (b, 1, h, w) and tuple(whole[1].shape) == (b, 4, h, w) and tuple(whole[2].shape) == (b, 2, h, w)
+    for what, a, e in zip(('out', 'stats', 'index'), by_rows, whole):
+        assert a.dtype == e.dtype and torch.equal(a, e), (name, variant, what, (a.double() - e.double()).abs().max().item())
+    for launch, got in (('contiguous', whole), ('rows', by_rows)):
+        check_multi(row, f'{name} S={len(moves)} {variant}', side, got, ref, d, cand_d, argmax, launch, cus)
+
+
+# ------------------------------------------------------------------ row 8: past the grid cap, all four kernels
+# local_pixel.h:105-110 -- past 16384 pixels a wave goes round ``pid += gridDim.x * 4`` again and reuses its LDS table, the `gathered`
+# flag and acc / cnt (depth_multi.hip:216, :353, :463, :600).  128 x 128 is the last one-trip map; 129 x 128 sends 32 workgroups round
+# again; at 2 x 91 x 91 sample 1 starts at pixel 8281, inside a workgroup, and 178 pixels are on the second trip.
+@pytest.mark.parametrize('variant', ['soft', 'argmax', 'use'])
+@pytest.mark.parametrize('name', [n for n in mv.BOUNDARY if n.startswith('cap-')])
+def test_grid_cap_multi_view_sweep(ops, cus, name, variant):
+    (b, h, w), d, moves = mv.BOUNDARY[name]
+    trips = db.pixel_grid_trips(b * h * w)
+    assert trips == (1 if b * h * w <= mv.GRID_PIXELS else 2) and int(mv.second_trip(b, h, w).sum()) == max(0, b * h * w - mv.GRID_PIXELS)
+    run_multi_case(ops, cus, '8 grid cap, multi-view sweep', name, variant, f'{trips} trip(s)')
+
+
+# ------------------------------------------------------------------ row 9: four to eight sources
+# The ABI takes S = 1 .. 8 (depth_multi.hip:665, :710): eight sources of which up to seven see a candidate, and five; under 'use' three
+# samples keep 1, 4 and 7 (of five: 5) sources.
+@pytest.mark.parametrize('variant', ['soft', 'use'])
+@pytest.mark.parametrize('name', [n for n in mv.BOUNDARY if n.startswith(('s8-', 's5-'))])
+def test_source_count_multi_view_sweep(ops, cus, name, variant):
+    (b, h, w), d, moves, use = mv.boundary_geometry(name, variant == 'use')
+    on = 'every source on' if use is None else 'sources on per sample ' + ' / '.join(str(int(n)) for n in use.sum(0))
+    run_multi_case(ops, cus, '9 source count, multi-view sweep', name, variant, f'{len(moves)} of 8 sources, {on}')
+
+
+def test_nine_sources_are_refused_by_both_entry_points(lib, cus):
+    """``sources = 9``: UM_ERR_UNSUPPORTED with a message from um_depth_corr_softmax_multi and um_depth_corr_softmax_multi_rows, the
+    output untouched (nothing was launched); eight sources on the same buffers are served."""
+    import ctypes
+    b, h, w, d = 1, 4, 5, 16
+    moves = mv.EIGHT + ('sideways',)
+    f0, f1 = (t.to(DEV) for t in mv.features(b, h, w, moves))
+    cam, cand = mv.cameras(b, h, w, moves).to(DEV), mv.candidates(d).to(DEV)
+    rows = torch.arange(9 * b, dtype=torch.int32).view(9, b, 1).repeat(1, 1, 3)
+    rows[..., 1] += 9 * b
+    rows = rows.to(DEV).contiguous()
+    tokens, table = torch.cat([f0.flatten(0, 1), f1.flatten(0, 1)], 0).contiguous(), cam.flatten(0, 1).contiguous()
+    ptrs, counts = (ctypes.c_void_p * 1)(tokens.data_ptr()), (ctypes.c_int * 1)(tokens.shape[0])
+    out = torch.full((b, 1, h, w), -7.0, device=DEV)
+    st = torch.cuda.current_stream().cuda_stream
+    p = lambda t: t.data_ptr()
+    calls = {
+        'um_depth_corr_softmax_multi': lambda s: lib.um_depth_corr_softmax_multi(p(f0), p(f1), p(cam), None, p(cand), p(out), None, None, s, b,
+                                                                                 h, w, C, d, 0, 1, st),
+        'um_depth_corr_softmax_multi_rows': lambda s: lib.um_depth_corr_softmax_multi_rows(ptrs, counts, 1, p(table), table.shape[0], p(rows),
+                                                                                           p(cand), p(out), None, None, s, b, h, w, C, d, 0, 1, st),
+    }
+    for what, call in calls.items():
+        rc = call(9)
+        assert rc == db.UM_ERR_UNSUPPORTED and b'sources=9' in lib.um_last_error_string(), (what, rc)
+        torch.cuda.synchronize()
+        assert bool((out == -7).all()), what
+        record('9 refusals', f'{what}, 9 sources', 'one step beyond', f'refused ({rc})', 0.0, 0.0, cus)
+    want = None
+    for what, call in calls.items():
+        out.fill_(-7.0)
+        assert call(8) == 0, what
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(out).all()) and bool((out != -7).all()), what
+        want = out.clone() if want is None else want
+        assert torch.equal(out, want)                                                # the table names the same operands in order
+
+
+# ------------------------------------------------------------------ row 10: the fourth segment and the segment edges
+# DepthSegments has four pointers (depth_multi.hip:416-431).  fu.scatter_edges: segments of 1, n, 1, m rows whose first and last rows
+# are all named, row ``total - 1`` and the off index ``total`` in neighbouring entries.  (Four shuffled segments at every case:
+# test_rows_launch_is_the_contiguous_launch of tests/test_depth_fuse_neighbours_gpu.py, and rows 8 and 9 above.)
+@pytest.mark.parametrize('argmax', [False, True])
+@pytest.mark.parametrize('case', ['B', 'C'])
+def test_segment_edges_and_the_fourth_segment(ops, cus, case, argmax):
+    (b, h, w), d, moves = mv.CASES[case]
+    f0, f1, cam, cand = mv.inputs(case)
+    segs, table, rows, use, ref = fu.edges_case(case)
+    total = sum(t.shape[0] for t in segs)
+    assert len(segs) == 4 and segs[0].shape[0] == segs[2].shape[0] == 1 and int(rows[..., :2].max()) == total
+    cand_d = cand.to(DEV)
+    whole = ops.depth_corr_softmax(f0.to(DEV), f1.to(DEV), h, w, cam.to(DEV), cand_d, argmax, stats=True, use=use.to(DEV))
+    by_rows = ops.depth_corr_softmax([t.to(DEV) for t in segs], None, h, w, table.to(DEV), cand_d, argmax, stats=True, rows=rows.to(DEV))
+    for what, a, e in zip(('out', 'stats', 'index'), by_rows, whole):
+        assert a.dtype == e.dtype and torch.equal(a, e), (case, what, (a.double() - e.double()).abs().max().item())
+    sizes = ' + '.join(str(t.shape[0]) for t in segs)
+    check_multi('10 segment edges, rows launch', f'case {case} {"argmax" if argmax else "soft"}, segments of {sizes} rows',
+                'first and last row of 4 segments', by_rows, ref, d, cand_d, argmax, 'rows', cus)
+
+
+# ------------------------------------------------------------------ row 11: every round of the gather form, sources that differ
+# acc[8] / cnt[8] of depth_multi_gather_kernel (depth_multi.hip:356-391): 96 candidates are six whole rounds, 113 one candidate past
+# seven, 128 the limit -- with three different sources, so that a count gone wrong in rounds 5 .. 7 does not cancel.
+@pytest.mark.parametrize('name', [n for n in mv.BOUNDARY if n.startswith('rounds-')])
+def test_gather_rounds_with_sources_that_differ(ops, cus, name):
+    (b, h, w), d, moves = mv.BOUNDARY[name]
+    f0, f1, cam, cand, _ = (t if t is None else t.to(DEV) for t in mv.boundary_inputs(name))
+    ref = mv.boundary_reference(name)
+    row, side = '11 gather rounds, sources that differ', f'{(d + 15) // 16} rounds, {d} of 128'
+    for argmax in (False, True):
+        got = ops.depth_corr_softmax(f0, f1, h, w, cam, cand, argmax, stats=True)
+        check_multi(row, f'{name} S={len(moves)} {"argmax" if argmax else "soft"}', side, got, ref, d, cand, argmax, 'contiguous', cus)
+    _, stats, _ = ops.depth_corr_softmax(f0, f1, h, w, cam, cand, stats=True, peak_radius=0)
+    off = (stats[:, 3].double() - stats[:, 0].double()).abs().max().item()
+    record(row, f'{name} peak_radius 0, peak_mass against max_prob', side, multi_kernel(d, 'contiguous'), off, mv.TOL, cus)
+    assert off <= mv.TOL
+    assert (stats[:, 0].cpu().double() - ref['stats'].max_prob).abs().max().item() <= mv.TOL
+    _, stats, _ = ops.depth_corr_softmax(f0, f1, h, w, cam, cand, stats=True, peak_radius=d)
+    off = (stats[:, 3].double() - 1.0).abs().max().item()
+    record(row, f'{name} peak_radius {d}, peak_mass against 1', side, multi_kernel(d, 'contiguous'), off, 1e-6, cus)
+    assert off <= 1e-6
