@@ -5,6 +5,12 @@ reference's per-layer device->host sync, transformer.py:55, is gone), so for a f
 once and replayed: at small batch the step is launch-bound (about 10 us of host time per launch), which is the
 regime of the reference's own evaluation protocol (batch 1).  ``GraphedUniMatch(model)`` behaves like the model;
 each distinct (shapes, keyword arguments) combination is captured on first use.
+
+A capture freezes the ADDRESSES of the weights' operand planes (buffers of ``HipOps._wcache``), while biases and LayerNorm
+parameters are read in place.  A graph is therefore valid for one state of the weights only -- the parameters' identity, address,
+version and dtype, the backend object and its ``cache_generation`` (which moves whenever a cache entry is built or the cache is
+dropped: ``invalidate_weights``, the prune) -- and is captured again, once, when that state has moved: after ``load_state_dict``,
+an in-place edit, ``.to()``, ``set_precision``.  Superseded graphs are released with their private pools and workspaces.
 """
 import contextlib
 import warnings
@@ -30,6 +36,20 @@ def _find_ops(model):
         if ops is not None and hasattr(ops, 'graph_scope'):
             return ops
         model = getattr(model, 'model', None) or getattr(model, 'module', None)
+    return None
+
+
+def _find_weights_state(model):
+    """``UniMatch.weights_state`` of the model inside the same wrappers; a module without one is walked parameter by parameter."""
+    seen, outer = set(), model
+    while model is not None and id(model) not in seen:
+        seen.add(id(model))
+        fn = getattr(model, 'weights_state', None)
+        if fn is not None:
+            return fn()
+        model = getattr(model, 'model', None) or getattr(model, 'module', None)
+    if hasattr(outer, 'parameters'):
+        return tuple((id(p), p.data_ptr(), p._version, p.dtype) for p in outer.parameters())
     return None
 
 
@@ -61,13 +81,30 @@ class GraphedUniMatch(torch.nn.Module):
                 static['out'] = self.model(static['img0'], static['img1'], **static['kw'])['flow_preds'][0]
         static['graph'] = graph
         static['workspaces'] = owned                # alive as long as the graph
+        static['state'] = self._state()             # after the warm-up: building the planes moved the cache generation
         return static
+
+    def _state(self):
+        """What a captured graph is valid for besides its key (see the module's docstring)."""
+        ops = _find_ops(self.model)
+        return (_find_weights_state(self.model), id(ops), getattr(ops, 'cache_generation', None))
+
+    def _release_superseded(self, state):
+        """Forget every graph of another weight state: nothing may replay it again, and its pool, static tensors and workspaces
+        would otherwise stay allocated until its own configuration is called the next time."""
+        for key in [k for k, e in self._graphs.items() if e is not False and e['state'] != state]:
+            del self._graphs[key]
 
     def forward(self, img0, img1, **kw):
         if not img0.is_cuda:
             return self.model(img0, img1, **kw)
         key = (tuple(img0.shape), tuple(img1.shape), str(img0.dtype), tuple(sorted((k, _freeze(v)) for k, v in kw.items())))
         entry = self._graphs.get(key)
+        if entry:
+            state = self._state()
+            if entry['state'] != state:
+                entry = None
+                self._release_superseded(state)
         if entry is None:
             try:
                 entry = self._capture(img0, img1, kw)

@@ -380,6 +380,7 @@ class UniMatch(nn.Module):
         self.debug_taps = None            # set to a dict to collect named intermediates (diagnostics only)
         self.check_weights = False        # True: fingerprint the parameters every forward (see _check_weight_print)
         self._weight_print = None
+        self._slots = None                # the submodules' parameter dicts (see _parameter_slots)
         self._runner = PartRunner()       # the batch as concurrent forwards (see forward)
 
     # ------------------------------------------------------------------ hot-path backend
@@ -402,7 +403,32 @@ class UniMatch(nn.Module):
         out = super()._apply(fn, *args, **kwargs)
         self.invalidate_weights()
         self._pos_cache = {}
+        self._slots = None
         return out
+
+    def _parameter_slots(self):
+        """The ``_parameters`` dicts of all submodules, collected once (``self.parameters()`` walks the module tree and builds every
+        name: some hundred microseconds, too much for a per-forward check).  The dicts are the modules' own: a parameter that is
+        assigned anew shows up here; ``.to()`` and friends collect them again."""
+        if self._slots is None:
+            self._slots = [m._parameters for m in self.modules() if m._parameters]
+        return self._slots
+
+    def weights_state(self):
+        """Identity, storage address, version and dtype of every parameter: what :meth:`HipOps._cache_get` keys a weight's planes by.
+        Equal states (together with an unchanged ``HipOps.cache_generation``) mean that the planes a captured graph reads are still
+        the planes of the current weights (``unimatch_amd.graph``)."""
+        return tuple((id(p), p.data_ptr(), p._version, p.dtype) for d in self._parameter_slots() for p in d.values() if p is not None)
+
+    def check_parameter_dtypes(self):
+        """The kernels read biases and LayerNorm parameters in place, as fp32, through their address: a parameter of another dtype
+        (``model.half()``) would be read past its end.  Weights are converted when their planes are built, but a model that is half
+        converted is refused as a whole, before any launch."""
+        for d in self._parameter_slots():
+            for name, p in d.items():
+                if p is not None and p.dtype is not torch.float32:
+                    raise ValueError(f'the HIP forward reads parameters as float32, found {name} {tuple(p.shape)} of dtype {p.dtype}: '
+                                     'convert the model with .float() (reduced precision is set_precision("fast"))')
 
     def load_state_dict(self, *args, **kwargs):
         out = super().load_state_dict(*args, **kwargs)
@@ -411,10 +437,12 @@ class UniMatch(nn.Module):
 
     def _check_weight_print(self):
         """check_weights=True: a per-forward fingerprint of all parameters (one fused norm, one host sync) that catches
-        in-place ``.data`` edits automatically -- off by default because the sync serialises back-to-back forwards."""
+        in-place ``.data`` edits automatically -- off by default because the sync serialises back-to-back forwards.  The first
+        fingerprint has nothing to be compared with: the planes that forwards before it cached (``check_weights`` switched on after
+        an edit) are dropped once."""
         params = [p.detach() for p in self.parameters()]
         fp = torch.stack(torch._foreach_norm(params)).double().cpu()
-        if self._weight_print is not None and not torch.equal(fp, self._weight_print):
+        if self._weight_print is None or not torch.equal(fp, self._weight_print):
             if self._ops is not None:
                 self._ops.invalidate_weights()
         self._weight_print = fp
@@ -668,6 +696,8 @@ class UniMatch(nn.Module):
         if len(attn_splits_list or ()) != 1 or len(prop_radius_list or ()) != 1:
             raise ValueError('forward_multiview: attn_splits_list and prop_radius_list need one entry (one scale)')
         ops = self.ops
+        if img_ref.is_cuda:
+            self.check_parameter_dtypes()
         if self.check_weights:
             self._check_weight_print()
         dev = img_ref.device
@@ -729,6 +759,8 @@ class UniMatch(nn.Module):
         if task not in self._PREDICT_DEFAULTS:
             raise ValueError(f'task must be one of {sorted(self._PREDICT_DEFAULTS)}, got {task!r}')
         factor, mode, kind = self._PREDICT_DEFAULTS[task]
+        if img0.is_cuda:
+            self.check_parameter_dtypes()                 # before the prepare launches, not only before the forward's
         shape = image_size(img0)
         if image_size(img1) != shape or img1.dtype != img0.dtype:
             raise ValueError(f'img0 {tuple(img0.shape)} {img0.dtype} and img1 {tuple(img1.shape)} {img1.dtype} differ')
@@ -971,6 +1003,8 @@ class UniMatch(nn.Module):
             from . import interp
         dev = frames.device
         ops = self.ops
+        if frames.is_cuda:
+            self.check_parameter_dtypes()
         if self.check_weights:
             self._check_weight_print()
         if frames.is_cuda and self.check_range and getattr(ops, 'mode', 1) == 0:
@@ -1096,6 +1130,8 @@ class UniMatch(nn.Module):
         from . import visualize
         dev = frames.device
         ops = self.ops
+        if frames.is_cuda:
+            self.check_parameter_dtypes()
         if self.check_weights:
             self._check_weight_print()
         if frames.is_cuda and self.check_range and getattr(ops, 'mode', 1) == 0:
@@ -1218,6 +1254,8 @@ class UniMatch(nn.Module):
         else:
             assert len(attn_splits_list) == len(corr_radius_list) == len(prop_radius_list) == self.num_scales
         ops = self.ops
+        if img0.is_cuda:
+            self.check_parameter_dtypes()
         if self.check_weights:
             self._check_weight_print()
         attn_type = attn_type if attn_type is not None else ''
