@@ -85,7 +85,7 @@ def conv_parts(kind, ho, wo):
     return 2 * ((ho + 7) // 8) * ((wo + 31) // 32) if kind == 'patch' else (ho * wo + 127) // 128
 
 
-NORM_CHUNK_ROWS, NORM_PARTS_IN_REGISTERS = 256, 1024      # nhwc_ops.hip:15, :74-75 (32 lanes x NB = 32 parts held in registers)
+NORM_CHUNK_ROWS, NORM_PARTS_IN_REGISTERS = 256, 1024      # nhwc_ops.hip:15, :86-87 (32 lanes x NB = 32 parts held in registers)
 
 
 # ------------------------------------------------------------------ the exported plan functions

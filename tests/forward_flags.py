@@ -92,10 +92,8 @@ def inputs(case):
     return i0, i1, cam
 
 
-@functools.lru_cache(maxsize=None)
-def _oracle(name, dtype):
-    case = BY_NAME[name]
-    i0, i1, cam = inputs(case)
+def run_oracle(case, i0, i1, cam, dtype):
+    """``oracle.model.unimatch_forward`` with the case's weights and flags on the given images (and camera) in ``dtype``, uncached."""
     kw = dict(case.fwd, num_scales=case.ctor['num_scales'], upsample_factor=case.ctor['upsample_factor'],
               reg_refine=case.ctor['reg_refine'], **{k: v.to(dtype) for k, v in cam.items()})
     before = torch.get_num_threads()
@@ -105,6 +103,12 @@ def _oracle(name, dtype):
             return om.unimatch_forward(state_dict(case), i0.to(dtype), i1.to(dtype), **kw)
     finally:
         torch.set_num_threads(before)
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(name, dtype):
+    case = BY_NAME[name]
+    return run_oracle(case, *inputs(case), dtype)
 
 
 def oracle(case, dtype=torch.float64):

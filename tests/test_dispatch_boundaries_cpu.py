@@ -215,7 +215,7 @@ def test_convolution_refuses_two_output_channels_on_the_host(lib):
 
 # ------------------------------------------------------------------ NHWC norm
 def test_norm_statistics_parts_of_the_gpu_rows():
-    """nhwc_ops.hip:15, 74-75: chunks of 256 pixels; up to 1024 parts stay in registers."""
+    """nhwc_ops.hip:15, 86-87: chunks of 256 pixels; up to 1024 parts stay in registers."""
     assert 512 * 512 // db.NORM_CHUNK_ROWS == db.NORM_PARTS_IN_REGISTERS and 513 * 512 // db.NORM_CHUNK_ROWS == db.NORM_PARTS_IN_REGISTERS + 2
 
 

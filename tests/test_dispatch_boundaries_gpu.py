@@ -726,7 +726,7 @@ def test_entry_kernel_follows_its_conditions(ops, lib, cus, cin, cout, supported
 
 
 # ================================================================== row 7: the two-pass statistics merge of the NHWC norm
-# nhwc_ops.hip:74-75 -- up to 32 x 32 = 1024 parts of 256 pixels stay in registers between the two sums; beyond, they are read twice.
+# nhwc_ops.hip:86-87 -- up to 32 x 32 = 1024 parts of 256 pixels stay in registers between the two sums; beyond, they are read twice.
 @pytest.mark.parametrize('hw', [(512, 512), (513, 512)])
 def test_norm_merge_at_1024_parts(ops, cus, hw):
     h, w = hw

@@ -29,11 +29,14 @@ assert MAX_FLOOR <= 1e-3
 ARGMAX_CAP, ARGMAX_TOL = 0.01, 1e-3
 
 
-def run_gpu(case, parts=1, timer=False, calls=1):
+def run_gpu(case, parts=1, timer=False, calls=1, images=None):
     """``calls`` forwards of the case in exact mode on one model -> (predictions on the CPU, {kernel name: launches} of all calls or
-    None).  ``parts``: the value of ``launch_parts`` (1: one forward of the whole batch)."""
+    None).  ``parts``: the value of ``launch_parts`` (1: one forward of the whole batch).  ``images``: ``(img0, img1)`` in place of
+    the case's own pair (tests/degenerate_content.py)."""
     model = ff.build_model(case).to(DEV).set_precision('exact')
     i0, i1, cam = ff.inputs(case)
+    if images is not None:
+        i0, i1 = images
     i0, i1, cam = i0.to(DEV), i1.to(DEV), {k: v.to(DEV) for k, v in cam.items()}
     model.launch_parts = parts
     if timer:
@@ -44,9 +47,14 @@ def run_gpu(case, parts=1, timer=False, calls=1):
     return [p.cpu() for p in preds], launches
 
 
-def sample_errors(case, pred):
+def _answers(case, answers):
+    """The (fp64, fp32) oracle answers the gates compare with: the case's own, or the pair handed in for other images."""
+    return answers if answers is not None else (ff.oracle(case, torch.float64), ff.oracle(case, torch.float32))
+
+
+def sample_errors(case, pred, answers=None):
     """Per sample: (mean, max) of |pred - fp64| and of |fp32 oracle - fp64|, as ``[(gpu_mean, gpu_max, f32_mean, f32_max), ...]``."""
-    truth, f32 = ff.oracle(case, torch.float64), ff.oracle(case, torch.float32)
+    truth, f32 = _answers(case, answers)
     assert pred.shape == truth.shape, (case.name, tuple(pred.shape), tuple(truth.shape))
     out = []
     for n in range(truth.shape[0]):
@@ -55,11 +63,12 @@ def sample_errors(case, pred):
     return out
 
 
-def check_gates(case, pred):
+def check_gates(case, pred, answers=None, tag=''):
+    """The module's gates on one prediction; ``answers``: the (fp64, fp32) oracle answers when the images are not the case's own."""
     assert torch.isfinite(pred).all(), case.name
-    truth, f32 = ff.oracle(case, torch.float64), ff.oracle(case, torch.float32)
-    figures = sample_errors(case, pred)
-    print(case.name, ' '.join(f'[{a:.2e} {b:.2e} | {c:.2e} {d:.2e}]' for a, b, c, d in figures))
+    truth, f32 = _answers(case, answers)
+    figures = sample_errors(case, pred, answers)
+    print(case.name + tag, ' '.join(f'[{a:.2e} {b:.2e} | {c:.2e} {d:.2e}]' for a, b, c, d in figures))
     for n, (g_mean, g_max, f_mean, f_max) in enumerate(figures):
         if case.fwd.get('depth_from_argmax'):
             d = (pred[n].double() - truth[n]).abs()

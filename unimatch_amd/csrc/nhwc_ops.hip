@@ -7,12 +7,17 @@
 // expects, and / or fp32 [rows][C] for a later shortcut).
 //
 // Statistics are deterministic and cancellation-safe: every workgroup reduces a chunk of pixels with a per-channel
-// shift (the chunk's first pixel), writing (shifted sum, shifted sum of squares); the finalize kernel merges the chunks
-// with the parallel-variance formula in fp64 and emits (mean, 1/sqrt(var + eps)) per (image, channel).
+// shift, writing (shifted sum, shifted sum of squares); the finalize kernel merges the chunks with the parallel-variance
+// formula in fp64 and emits (mean, 1/sqrt(var + eps)) per (image, channel).  The shift is the median of the chunk's
+// first, middle and last pixel: one outlier cannot become the shift.  (With the first pixel alone as the shift, a
+// single pixel of 1000 in a plane of N(0, 1) made every shifted value about -1000, and sum((x - k)^2) - sum(x - k)^2 / n
+// cancelled 2.5e8 against 2.5e8 in fp32 sums: the outlier's z-score came out 4e-5 relative off.)
 #include "common.h"
 #include "planes.h"
 
 #define NHWC_CHUNK_ROWS 256
+
+__device__ __forceinline__ float med3(float a, float b, float c) { return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c)); }
 
 // ---- pass 1: per-chunk shifted sums.  grid (chunks, B), block 256; thread = (row lane, channel quad) --------------
 __global__ __launch_bounds__(256) void nhwc_stats_kernel(const float* x, float* partial, int P, int C, int nchunk) {
@@ -21,10 +26,16 @@ __global__ __launch_bounds__(256) void nhwc_stats_kernel(const float* x, float* 
     const int quads = C >> 2, rl_n = 256 / quads;
     const int q = threadIdx.x % quads, rl = threadIdx.x / quads;
     const int r0 = ch * NHWC_CHUNK_ROWS, r1 = min(P, r0 + NHWC_CHUNK_ROWS);
+    const int rm = r0 + ((r1 - r0) >> 1);                           // the shift: median of rows r0, rm, r1 - 1 (they may coincide)
     const float* xb = x + ((long)b * P) * C + 4 * q;
     f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1;
     if (rl < rl_n) {
-        const f32x4 k = *reinterpret_cast<const f32x4*>(xb + (long)r0 * C);
+        const f32x4 ka = *reinterpret_cast<const f32x4*>(xb + (long)r0 * C);
+        const f32x4 kb = *reinterpret_cast<const f32x4*>(xb + (long)rm * C);
+        const f32x4 kc = *reinterpret_cast<const f32x4*>(xb + (long)(r1 - 1) * C);
+        f32x4 k;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) k[i] = med3(ka[i], kb[i], kc[i]);
         for (int r = r0 + rl; r < r1; r += rl_n) {
             const f32x4 v = *reinterpret_cast<const f32x4*>(xb + (long)r * C) - k;
             s1 += v;
@@ -46,7 +57,8 @@ __global__ __launch_bounds__(256) void nhwc_stats_kernel(const float* x, float* 
             a2 += red[1][(l * quads + cq) * 4 + ci];
         }
         float* pr = partial + (((long)b * nchunk + ch) * 3) * C;
-        pr[c] = x[((long)b * P + r0) * C + c];                    // the shift
+        const float* xc = x + ((long)b * P) * C + c;
+        pr[c] = med3(xc[(long)r0 * C], xc[(long)rm * C], xc[(long)(r1 - 1) * C]);      // the shift, as every row lane took it
         pr[C + c] = a1;
         pr[2 * C + c] = a2;
     }
