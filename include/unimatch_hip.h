@@ -42,7 +42,9 @@ extern "C" {
 #endif
 
 #define UM_VERSION 220   /* 220 also gained um_global_match_stats_workspace_bytes, um_global_match_stats and um_match_mutual,
-                            um_depth_corr_softmax_multi, um_depth_corr_softmax_multi_rows */
+                            um_depth_corr_softmax_multi, um_depth_corr_softmax_multi_rows, and the TSDF fusion entry points
+                            um_tsdf_integrate, um_tsdf_points_workspace_bytes and um_tsdf_points (additions only: no existing
+                            entry point changed, so the number stays) */
 
 #define UM_MODE_EXACT 0
 #define UM_MODE_FAST 1
@@ -847,6 +849,57 @@ size_t um_points_workspace_bytes(int batch, int h, int w, int stride);
 int um_points_pack(const float* depth, const float* cam_world, const float* keep, const unsigned char* colors, float* xyz,
                    unsigned char* rgb, int* count, int batch, int h, int w, int stride, float min_depth, float max_depth, void* workspace,
                    size_t ws_bytes, void* stream);
+
+/* Volumetric fusion of posed depth maps (csrc/fusion.hip): a truncated signed distance (TSDF) volume averages the depths of all views,
+ * weighted, and yields ONE surface at a size that does not grow with the video.  One thread per voxel; both entry points
+ * enqueue on `stream`, never synchronise, use no atomics and keep nothing between calls; fp32 arithmetic with every product, sum and
+ * quotient rounded on its own: each is bitwise equal to its host restatement (unimatch_amd/fusion.py).
+ * Volume state (caller-owned, fp32, contiguous, x fastest): tsdf [nz,ny,nx] in units of the truncation distance, in [-1, 1]; weight
+ * [nz,ny,nx] >= 0; color [3,nz,ny,nx] (optional planes, running means in 0..255).  A fresh volume is all zeros.  Voxel (i, j, k) has
+ * the world centre X = (ox + (float)i voxel, oy + (float)j voxel, oz + (float)k voxel), origin = {ox, oy, oz} a HOST array read before
+ * the call returns.  nx * ny * nz < 2^31.  A null pointer (where not stated as optional), a non-positive size, voxel / trunc /
+ * max_weight not greater than 0 (or NaN), a colour pointer without its partner or an oversized volume returns UM_ERR_BAD_ARG and names
+ * the entry point in um_last_error_string, before any device call.  No input value -- NaN, infinity, a singular camera -- causes an
+ * out-of-bounds access: taps are read from clamped addresses and discarded.
+ *   um_tsdf_integrate   depth [B,H,W] fp32 METRIC; cam_view [B][30] the WORLD-TO-CAMERA records: the second half of a bidirectional
+ *                       um_depth_cam_pack of the intrinsics and the camera-to-world pose at stride_div = 1; weight_in [B,H,W] fp32 or
+ *                       NULL (= 1); colors [B,H,W,3] uint8, NULL exactly when color is NULL.  B * H * W < 2^31.  ONE launch for all B
+ *                       views: each voxel is owned by one thread that applies the views in ascending b with the running state in
+ *                       registers, so the volume is read once and written once per call whatever B is, and one B-view call equals B
+ *                       one-view calls bit for bit.  A voxel that no view updated is not written.  Per voxel (x, y, z) and view, with
+ *                       c = cam_view[b]:
+ *                          1. Xc_r = c[9+3r] x + c[10+3r] y + c[11+3r] z + c[18+r], summed left to right (r = 0, 1, 2);
+ *                          2. zz = c[27] Xc_0 + c[28] Xc_1 + c[29] Xc_2; skip the view unless zz > 1e-3;
+ *                          3. u = (c[21] Xc_0 + c[22] Xc_1 + c[23] Xc_2) / zz, v likewise with c[24..26];
+ *                          4. px = rintf(u), py = rintf(v): the NEAREST pixel (interpolating depth across a discontinuity would
+ *                             invent surfaces);
+ *                          5. skip unless 0 <= px <= W - 1 and 0 <= py <= H - 1 (a NaN position skips);
+ *                          6. d = depth[b, py, px]; skip unless d is finite and min_depth < d < max_depth;
+ *                          7. w = weight_in ? weight_in[b, py, px] : 1; skip unless w is finite and w > 0;
+ *                          8. sdf = d - Xc_2; skip unless sdf >= -trunc (so a NaN skips too);
+ *                          9. f = fminf(1, sdf / trunc);
+ *                         10. Wn = W + w, tsdf = (tsdf W + f w) / Wn;
+ *                         11. each colour plane: C = (C W + (float)colors[b, py, px, ch] w) / Wn;
+ *                         12. W = fminf(Wn, max_weight).
+ *   um_tsdf_points      the surface points of the volume, in a deterministic order: candidates in ascending (k, j, i), then by axis
+ *                       x, y, z.  The candidate of voxel p and axis a is the edge from p to its neighbour n = p + e_a where that
+ *                       neighbour is inside the volume; it is a crossing iff weight(p) >= min_weight and weight(n) >= min_weight,
+ *                       (tp < 0) != (tn < 0), and fabsf(tp) < 1 and fabsf(tn) < 1 (the last drops free-space-to-unseen jumps at
+ *                       occlusion borders).  With s = tp / (tp - tn) its point is X(p) with coordinate a increased by s voxel, and its
+ *                       colour rint(Cp + s (Cn - Cp)) clamped to 0..255.  xyz [capacity,3] fp32, rgb [capacity,3] uint8 (rgb given
+ *                       exactly when color is).  A STABLE compaction built as um_points_pack is: per-workgroup counts (wave-64 ballot
+ *                       + popcount) into `workspace`, one workgroup's exclusive scan, a scatter at scanned offset + rank; every
+ *                       workspace slot that is read was written by the same call.  count (one int32 ON THE DEVICE) always receives
+ *                       the full N (N < 2^31 is assumed); rows n >= capacity are not written: the caller runs again with a larger
+ *                       buffer when N > capacity (capacity >= 0).  workspace (4-byte aligned) >=
+ *                       um_tsdf_points_workspace_bytes(nx, ny, nz) (0 for bad sizes), else UM_ERR_WORKSPACE. */
+int um_tsdf_integrate(const float* depth, const float* cam_view, const float* weight_in, const unsigned char* colors, float* tsdf,
+                      float* weight, float* color, int nx, int ny, int nz, const float* origin, float voxel, float trunc,
+                      float max_weight, float min_depth, float max_depth, int batch, int h, int w, void* stream);
+size_t um_tsdf_points_workspace_bytes(int nx, int ny, int nz);
+int um_tsdf_points(const float* tsdf, const float* weight, const float* color, int nx, int ny, int nz, const float* origin, float voxel,
+                   float min_weight, float* xyz, unsigned char* rgb, int* count, int capacity, void* workspace, size_t ws_bytes,
+                   void* stream);
 
 /* Frame synthesis from flow (csrc/interp.hip): apply a flow to the frames it was computed from.  A classical synthesis with no learned
  * part.  Memory-bound, one thread per pixel; every entry point enqueues on `stream` and never synchronises; nothing is kept between

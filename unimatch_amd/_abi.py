@@ -113,6 +113,11 @@ SIGNATURES = {
     'um_depth_consistency': (_c_int, [_c_void_p] * 7 + [_c_int] * 3 + [ctypes.c_float] * 2 + [_c_void_p]),
     'um_points_workspace_bytes': (_c_size_t, [_c_int] * 4),
     'um_points_pack': (_c_int, [_c_void_p] * 7 + [_c_int] * 4 + [ctypes.c_float] * 2 + [_c_void_p, _c_size_t, _c_void_p]),
+    'um_tsdf_integrate': (_c_int, [_c_void_p] * 7 + [_c_int] * 3 + [ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 5 + [_c_int] * 3 +
+                          [_c_void_p]),
+    'um_tsdf_points_workspace_bytes': (_c_size_t, [_c_int] * 3),
+    'um_tsdf_points': (_c_int, [_c_void_p] * 3 + [_c_int] * 3 + [ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 2 + [_c_void_p] * 3 +
+                       [_c_int, _c_void_p, _c_size_t, _c_void_p]),
     'um_instance_norm_fwd': (_c_int, [_c_void_p] * 3 + [ctypes.c_long, _c_int, ctypes.c_float, _c_int, _c_void_p]),
     'um_global_corr_workspace_bytes': (_c_size_t, [_c_int] * 4),
     'um_global_corr_softmax_flow': (_c_int, [_c_void_p] * 3 + [_c_int] * 6 + [_c_void_p, _c_size_t, _c_void_p]),

@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libunimatch_hip.so')
 SOURCES = ['capi.hip', 'global_match.hip', 'window_attn.hip', 'local_ops.hip', 'linear.hip', 'ffn.hip', 'conv.hip', 'nhwc_ops.hip', 'norm_ops.hip', 'upsample.hip',
            'rccl_gather.hip', 'local_corr_mfma.hip', 'aliases.hip', 'probe.hip', 'video.hip', 'metrics.hip', 'prepost.hip', 'visualize.hip', 'geometry.hip', 'match_stats.hip',
-           'interp.hip', 'depth_multi.hip']
+           'interp.hip', 'depth_multi.hip', 'fusion.hip']
 # hardware micro-benchmarks (um_debug_*): diagnostic builds only, never in the shipped library
 DIAG_SOURCES = ['microbench.hip']
 HEADERS = ['common.h', 'planes.h', 'timing.h', 'local_pixel.h', os.path.join('..', '..', 'include', 'unimatch_hip.h')]
@@ -33,6 +33,8 @@ EXTRA_FLAGS = {'ffn.hip': ['-fno-slp-vectorize'], 'global_match.hip': ['-fno-slp
                'geometry.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
                # ... and the frame-synthesis kernels theirs: bit for bit, integer accumulators included
                'interp.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
+               # ... and the TSDF fusion kernels theirs: the running averages of a voxel, bit for bit
+               'fusion.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
                # the confidence kernel's final quotients are IEEE: a row with one key gives max_prob = l / l = 1 exactly
                'match_stats.hip': ['-fno-slp-vectorize', '-fhip-fp32-correctly-rounded-divide-sqrt', '-Wno-inline-asm']}
 # kernels that sit at the register limit of their occupancy (conv_entry_kernel<Fp16, 2, 4>: all 256 VGPRs of two workgroups per CU): the
@@ -52,7 +54,10 @@ RESOURCE_GUARDS = {'conv.hip': {'conv_entry_kernel': 2},
                    # the confidence kernel is laid out for two workgroups per CU (64 KB of LDS each in exact mode); the mutual check is per-pixel
                    'match_stats.hip': {'match_stats_kernel': 2, 'match_mutual_kernel': 4},
                    # per-pixel gather / scatter kernels: memory- and atomic-bound, no scratch (the times are indexed in the kernel arguments)
-                   'interp.hip': {'image_warp_kernel': 4, 'flow_splat_kernel': 4, 'splat_normalize_kernel': 4, 'frame_synth_kernel': 4}}
+                   'interp.hip': {'image_warp_kernel': 4, 'flow_splat_kernel': 4, 'splat_normalize_kernel': 4, 'frame_synth_kernel': 4},
+                   # memory-bound per-voxel kernels, as the per-pixel ones of geometry.hip: no scratch, no wave lost to registers
+                   'fusion.hip': {'tsdf_integrate_kernel': 4, 'tsdf_points_count_kernel': 4, 'tsdf_points_scan_kernel': 4,
+                                  'tsdf_points_scatter_kernel': 4}}
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result']
 
 

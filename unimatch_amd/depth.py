@@ -31,11 +31,17 @@ Values and geometry (both modes write the same files):
                             ``--pred-bidir-depth`` the last frame's depth is the last pair's backward prediction: the pairwise mode
                             filters it on that prediction's own ``peak_mass``, ``--pairs-per-launch`` keeps the forward maps only
                             and leaves that one frame to the consistency check alone, so the two modes' clouds can differ in it
+  ``--save-tsdf-ply FILE``  the TSDF surface of the whole scene (binary PLY): the same depths and colours fused in one voxel grid of
+                            ``--voxel-size`` metres (:func:`unimatch_amd.fusion.fuse_depth_sequence_tsdf`), truncation
+                            ``--tsdf-trunc`` (default: 4 voxels), the surface taken between voxels of weight ``>= --tsdf-min-weight``.
+                            The integration weight is the ``keep`` mask of the point cloud -- consistency, plus ``--min-confidence``
+                            when given -- so the surface is made of exactly the pixels ``--save-ply`` keeps, averaged across frames
+                            instead of concatenated; it needs no ``--save-ply``
 
 Frame i has a depth map through the pair (i, i + 1); the last frame has one only with ``--pred-bidir-depth``, through the last pair's
 backward prediction, and gets its ``_depth.png`` / ``_occ.png`` then.  The geometry always uses the depth restored to the frames' own
-size with the scene's own intrinsics, whatever ``--scale-intrinsics`` gave the model.  For ``--consistency-check`` and ``--save-ply`` the
-runner keeps the restored depth maps and the uint8 frames of the whole scene resident on the device -- 4 + 3 bytes per pixel and frame
+size with the scene's own intrinsics, whatever ``--scale-intrinsics`` gave the model.  For ``--consistency-check``, ``--save-ply`` and
+``--save-tsdf-ply`` the runner keeps the restored depth maps and the uint8 frames of the whole scene resident on the device -- 4 + 3 bytes per pixel and frame
 -- and fuses after the last piece (all frames of one size).
 """
 import argparse
@@ -70,16 +76,17 @@ def relative_pose(pose_ref, pose_tgt):
 
 
 class _SceneCollector:
-    """What ``--save-depth``, ``--consistency-check`` and ``--save-ply`` need of a scene: writes each restored depth map as it
+    """What ``--save-depth``, ``--consistency-check``, ``--save-ply`` and ``--save-tsdf-ply`` need of a scene: writes each restored depth map as it
     arrives and, for the latter two, keeps it and its uint8 frame on the device until :meth:`finish` fuses the scene."""
 
     def __init__(self, out_dir, imgs, poses, k, save_depth, consistency_check, save_ply, ply_stride, min_views, px_thr, rel_thr,
-                 min_confidence=None):
+                 min_confidence=None, save_tsdf_ply=None, voxel_size=0.04, tsdf_trunc=None, tsdf_min_weight=1.):
         self.min_confidence, self.conf = min_confidence, []
+        self.save_tsdf_ply, self.voxel_size, self.tsdf_trunc, self.tsdf_min_weight = save_tsdf_ply, voxel_size, tsdf_trunc, tsdf_min_weight
         self.out_dir, self.imgs, self.poses, self.k = out_dir, imgs, poses, k
         self.save_depth, self.consistency_check, self.save_ply = save_depth, consistency_check, save_ply
         self.ply_stride, self.min_views, self.px_thr, self.rel_thr = ply_stride, min_views, px_thr, rel_thr
-        self.fuse = bool(consistency_check or save_ply)
+        self.fuse = bool(consistency_check or save_ply or save_tsdf_ply)
         self.depths, self.frames = [], []
 
     def stem(self, i):
@@ -96,7 +103,7 @@ class _SceneCollector:
             assert i == len(self.depths)
             if self.depths and depth.shape != self.depths[0].shape:
                 raise ValueError(f'{self.imgs[i]} is {tuple(depth.shape)}, the scene began with {tuple(self.depths[0].shape)}: '
-                                 '--consistency-check / --save-ply need frames of one size')
+                                 '--consistency-check / --save-ply / --save-tsdf-ply need frames of one size')
             self.depths.append(depth)
             self.frames.append(frame_u8)
             if self.min_confidence is not None:
@@ -109,7 +116,7 @@ class _SceneCollector:
             return
         n = len(self.depths)
         if n < 2:
-            raise ValueError(f'--consistency-check / --save-ply need at least two frames with a depth map, the scene gave {n}')
+            raise ValueError(f'--consistency-check / --save-ply / --save-tsdf-ply need at least two frames with a depth map, the scene gave {n}')
         depths, colors = torch.stack(self.depths, 0), torch.stack(self.frames, 0)
         dev = depths.device
         out = fuse_depth_sequence(depths, torch.from_numpy(self.k)[None].to(dev), torch.from_numpy(self.poses[:n]).to(dev), colors,
@@ -122,24 +129,35 @@ class _SceneCollector:
                 write_png8(self.stem(i) + '_occ.png', occ[i])
         if self.save_ply:
             write_ply(self.save_ply, out['xyz'].cpu().numpy(), out['rgb'].cpu().numpy())
+        if self.save_tsdf_ply:
+            from .fusion import fuse_depth_sequence_tsdf
+            if not bool(out['keep'].any()):                    # nothing is kept: an empty surface, as --save-ply writes an empty cloud
+                write_ply(self.save_tsdf_ply, np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8))
+                return
+            surf = fuse_depth_sequence_tsdf(depths, torch.from_numpy(self.k)[None].to(dev), torch.from_numpy(self.poses[:n]).to(dev), colors,
+                                            weight=out['keep'], voxel_size=self.voxel_size, trunc=self.tsdf_trunc,
+                                            min_weight=self.tsdf_min_weight)
+            write_ply(self.save_tsdf_ply, surf['xyz'].cpu().numpy(), surf['rgb'].cpu().numpy())
 
 
 def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_size=None, min_depth=0.5, max_depth=10.,
               num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, scale_intrinsics=False, device='cuda',
               pairs_per_launch=None, save_depth=False, consistency_check=False, save_ply=None, ply_stride=1, min_views=1, px_thr=1.0,
-              rel_thr=0.01, save_confidence=False, min_confidence=None, peak_radius=1, fuse_neighbours=False):
+              rel_thr=0.01, save_confidence=False, min_confidence=None, peak_radius=1, fuse_neighbours=False, save_tsdf_ply=None,
+              voxel_size=0.04, tsdf_trunc=None, tsdf_min_weight=1.):
     """``inference_depth`` over the scene: returns the number of frames written (one less than the scene has).
     ``pairs_per_launch=N``: sequence mode (the module docstring), in pieces of N pairs; ``None``: one ``predict`` per pair.
     ``save_depth``, ``consistency_check``, ``save_ply`` (a file name): the value and geometry outputs of the module docstring.
-    ``save_confidence``, ``min_confidence`` (with ``save_ply``), ``peak_radius``: the plane sweep's confidence, taken in the forward's
+    ``save_tsdf_ply`` (a file name), ``voxel_size``, ``tsdf_trunc``, ``tsdf_min_weight``: the TSDF surface of the scene.
+    ``save_confidence``, ``min_confidence`` (with ``save_ply`` or ``save_tsdf_ply``), ``peak_radius``: the plane sweep's confidence, taken in the forward's
     own matching launch (``forward_with_depth_confidence`` / ``forward_sequence(return_confidence=True)``).
     ``fuse_neighbours`` (sequence mode only, not with ``pred_bidir_depth``): the previous frame votes in every frame's plane sweep
     (``forward_sequence(fuse_neighbours=True)``: an unlearned two-source fusion for the price of the sweep; the files are the same)."""
     from .confidence import confidence_to_image, confidence_to_image_size
     from .io import write_png8
     from .prepost import InferenceGeometry
-    if min_confidence is not None and not save_ply:
-        raise ValueError('min_confidence filters the point cloud: it needs save_ply')
+    if min_confidence is not None and not (save_ply or save_tsdf_ply):
+        raise ValueError('min_confidence filters the point cloud: it needs save_ply or save_tsdf_ply')
     if fuse_neighbours and pairs_per_launch is None:
         raise ValueError('fuse_neighbours is an option of the sequence mode: it needs pairs_per_launch')
     if fuse_neighbours and pred_bidir_depth:
@@ -148,9 +166,11 @@ def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_si
     imgs, poses, k = read_scene(scene_dir)
     os.makedirs(out_dir, exist_ok=True)
     collect = None
-    if save_depth or consistency_check or save_ply:
+    if save_depth or consistency_check or save_ply or save_tsdf_ply:
         collect = _SceneCollector(out_dir, imgs, poses, k, save_depth, consistency_check, save_ply, int(ply_stride), int(min_views),
-                                  float(px_thr), float(rel_thr), None if min_confidence is None else float(min_confidence))
+                                  float(px_thr), float(rel_thr), None if min_confidence is None else float(min_confidence),
+                                  save_tsdf_ply, float(voxel_size), None if tsdf_trunc is None else float(tsdf_trunc),
+                                  float(tsdf_min_weight))
     skip = ('task', 'min_depth', 'max_depth', 'num_depth_candidates', 'depth_from_argmax', 'pred_bidir_depth', 'intrinsics', 'pose',
             'poses')
     fwd_kw = {key: v for key, v in fwd_kw.items() if key not in skip}
@@ -292,12 +312,18 @@ def main(argv=None):
     ap.add_argument('--consistency-check', action='store_true', help='write <stem>_occ.png: 255 where the neighbouring frames disagree')
     ap.add_argument('--save-ply', default=None, metavar='FILE', help='write the fused, filtered, coloured point cloud of the scene')
     ap.add_argument('--ply-stride', type=int, default=1, metavar='S', help='every S-th pixel of every row and column goes into the cloud')
+    ap.add_argument('--save-tsdf-ply', default=None, metavar='FILE',
+                    help='write the TSDF surface of the scene: the pixels --save-ply keeps, fused in one voxel grid')
+    ap.add_argument('--voxel-size', type=float, default=0.04, metavar='M', help='with --save-tsdf-ply: the edge of a voxel in metres')
+    ap.add_argument('--tsdf-trunc', type=float, default=None, metavar='M', help='with --save-tsdf-ply: the truncation distance (default: 4 voxels)')
+    ap.add_argument('--tsdf-min-weight', type=float, default=1., metavar='W',
+                    help='with --save-tsdf-ply: the surface is taken between voxels of at least this accumulated weight')
     ap.add_argument('--min-views', type=int, default=1, help='neighbouring frames (of two) that must agree with a pixel to keep it')
     ap.add_argument('--px-thr', type=float, default=1.0, help='round-trip reprojection error a consistent pixel stays below (pixels)')
     ap.add_argument('--rel-thr', type=float, default=0.01, help='relative depth error a consistent pixel stays below')
     ap.add_argument('--save-confidence', action='store_true', help="write <stem>_conf.png: the plane sweep's max_prob, coloured")
     ap.add_argument('--min-confidence', type=float, default=None, metavar='P',
-                    help='with --save-ply: keep a pixel only where the probability mass around its best depth candidate is >= P '
+                    help='with --save-ply / --save-tsdf-ply: keep a pixel only where the probability mass around its best depth candidate is >= P '
                          '(with --pairs-per-launch and --pred-bidir-depth the last frame, seen backward, is not filtered on it)')
     ap.add_argument('--peak-radius', type=int, default=1, metavar='R', help='candidates each side of the best one that count as its peak')
     ap.add_argument('--model-config', default='gmdepth_s1', choices=[k for k, v in CONFIGS.items() if v[1].get('task') == 'depth'])
@@ -316,7 +342,8 @@ def main(argv=None):
                   scale_intrinsics=args.scale_intrinsics, pairs_per_launch=args.pairs_per_launch, save_depth=args.save_depth,
                   consistency_check=args.consistency_check, save_ply=args.save_ply, ply_stride=args.ply_stride, min_views=args.min_views,
                   px_thr=args.px_thr, rel_thr=args.rel_thr, save_confidence=args.save_confidence, min_confidence=args.min_confidence,
-                  peak_radius=args.peak_radius, fuse_neighbours=args.fuse_neighbours)
+                  peak_radius=args.peak_radius, fuse_neighbours=args.fuse_neighbours, save_tsdf_ply=args.save_tsdf_ply,
+                  voxel_size=args.voxel_size, tsdf_trunc=args.tsdf_trunc, tsdf_min_weight=args.tsdf_min_weight)
     print(f'{n} frames written to {args.out}')
 
 

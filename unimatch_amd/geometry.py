@@ -10,6 +10,10 @@
   fuse_depth_sequence(depths, intrinsics, poses, colors, ..)           every frame of a posed video checked against its neighbours,
                                                                        the consistent pixels fused into one cloud
 
+``fuse_depth_sequence`` concatenates: every kept pixel of every frame is a point of its own.  Volumetric fusion of the same depths --
+one voxel grid that averages them across frames, with ``keep`` or a confidence as the weight -- is :mod:`unimatch_amd.fusion`
+(``TSDFVolume``, ``fuse_depth_sequence_tsdf``; ``csrc/fusion.hip``), which takes its bounds from ``back_project_points``.
+
 CUDA tensors run on the HIP kernels of ``csrc/geometry.hip`` (``um_disp_consistency``, ``um_depth_consistency``, ``um_points_pack``),
 with the camera records of ``um_depth_cam_pack`` and the relative poses of ``um_relative_pose_pairs``: no ``torch.inverse``, no
 ``grid_sample``, no boolean indexing, and one host synchronisation per cloud (the read of the point count).  Host tensors run the
