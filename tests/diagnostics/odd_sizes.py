@@ -1,7 +1,10 @@
 """Diagnostic (GPU box): the channels-last convolution path against the stock nn.Conv2d (MIOpen) path of the same module on
 image sizes that do not tile nicely (statistics fallback, ragged tiles, row-window kernel borders), next to the spread
-between two other numerically equivalent evaluations (two-launch FFN, separate merge kernel) -- the two-scale + refinement
-configs are chaotic at random-init weights, so only the comparison with that spread is meaningful.
+between two other numerically equivalent evaluations (two-launch FFN, separate merge kernel), at dataset sizes (448x1024,
+384x1248) and random-init weights -- where the two-scale + refinement configs are chaotic, so this script can only compare device
+variants with each other.  The TEST of whole forwards at sizes that do not tile is tests/test_forward_sizes_gpu.py: ``CONDITIONED``
+weights make the fp64 oracle a meaningful reference there, at small ragged, odd-window, portrait and tiny sizes
+(tests/forward_sizes.py), with the launch census asserting which kernels ran.
     python tests/diagnostics/odd_sizes.py"""
 import os
 import sys
