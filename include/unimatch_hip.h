@@ -43,8 +43,8 @@ extern "C" {
 
 #define UM_VERSION 220   /* 220 also gained um_global_match_stats_workspace_bytes, um_global_match_stats and um_match_mutual,
                             um_depth_corr_softmax_multi, um_depth_corr_softmax_multi_rows, and the TSDF fusion entry points
-                            um_tsdf_integrate, um_tsdf_points_workspace_bytes and um_tsdf_points (additions only: no existing
-                            entry point changed, so the number stays) */
+                            um_tsdf_integrate, um_tsdf_points_workspace_bytes, um_tsdf_points, um_tsdf_mesh_workspace_bytes and
+                            um_tsdf_mesh (additions only: no existing entry point changed, so the number stays) */
 
 #define UM_MODE_EXACT 0
 #define UM_MODE_FAST 1
@@ -900,6 +900,49 @@ size_t um_tsdf_points_workspace_bytes(int nx, int ny, int nz);
 int um_tsdf_points(const float* tsdf, const float* weight, const float* color, int nx, int ny, int nz, const float* origin, float voxel,
                    float min_weight, float* xyz, unsigned char* rgb, int* count, int capacity, void* workspace, size_t ws_bytes,
                    void* stream);
+
+/* The triangle mesh of a TSDF volume (csrc/tsdf_mesh.hip): marching tetrahedra on the Kuhn split of every cell -- six tetrahedra around
+ * the main diagonal, the same split in every cell, so neighbouring cells agree on every face diagonal and the mesh is watertight by
+ * construction; no case table, no ambiguous case.  Volume state, grid, argument rules and the bitwise agreement with the host
+ * restatement (unimatch_amd/fusion.py: extract_mesh_host) are those of um_tsdf_points; the call enqueues on `stream`, never
+ * synchronises, uses no atomics and keeps nothing.  A corner or edge mask m in 0..7 has bit 0 = +x, bit 1 = +y, bit 2 = +z; p + m adds
+ * those unit steps to the voxel p = (i, j, k); t(p), w(p) are its stored value and weight.
+ *   valid voxel    w(p) >= min_weight and fabsf(t(p)) < 1 (false for NaN): the rule of um_tsdf_points.
+ *   active cell    cell c = (i, j, k) with i < nx - 1, j < ny - 1, k < nz - 1 whose eight corners c + m are all valid.
+ *   inside         t < 0; a stored 0 counts as outside.
+ *   edges          voxel p owns the seven edges (p, e), e = 1..7, from p to p + e: three axis edges (1, 2, 4), three face diagonals
+ *                  (3, 5, 6), the body diagonal (7).  Edge (p, e) lies in the cells p - s for every subset s of the bits not in e
+ *                  (those inside the grid), and carries a vertex when (t(p) < 0) != (t(p + e) < 0) and at least one of its cells is
+ *                  active: no vertex is unreferenced.
+ *   vertex         s = tp / (tp - tn) with tp = t(p), tn = t(p + e); coordinate a is base_a + s voxel where bit a is set in e, else
+ *                  base_a, base = (ox + (float)i voxel, ...); colour rint(Cp + s (Cn - Cp)) clamped to 0..255, NaN -> 0.  For e in
+ *                  {1, 2, 4} the vertex is bit for bit the point um_tsdf_points emits for that edge.
+ *   vertex order   ascending (k, j, i, e).
+ *   tetrahedra     tetrahedron tau = 0..5 of a cell belongs to the permutation pi of (0, 1, 2), in lexicographic order (0,1,2) (0,2,1)
+ *                  (1,0,2) (1,2,0) (2,0,1) (2,1,0), of sign sigma = + - - + + -.  Its corners are the masks v0 = 0, v1 = 1 << pi0,
+ *                  v2 = v1 | 1 << pi1, v3 = 7; the edge between vq and vr (q < r) is the owned edge (c + vq, vr ^ vq), its vertex
+ *                  index E(q, r) = E(r, q).
+ *   faces          per tetrahedron, I the inside positions ascending, O the outside positions ascending:
+ *                    |I| = 0 or 4   no face;
+ *                    |I| = 1, a = I[0]: the triangle (E(a,O0), E(a,O1), E(a,O2)), reversed iff (sigma > 0) == (a odd);
+ *                    |I| = 3, a = O[0]: the triangle (E(a,I0), E(a,I1), E(a,I2)), reversed iff NOT ((sigma > 0) == (a odd));
+ *                    |I| = 2, a < b inside, c < d outside: the quad q = (E(a,c), E(a,d), E(b,d), E(b,c)) as (q0,q1,q2) and (q0,q2,q3),
+ *                                   both reversed iff (sigma > 0) == ((a + b) even);
+ *                  reversed: (x, y, z) -> (z, y, x).  Every face is then counter-clockwise seen from free space (t > 0).
+ *   face order     ascending (k, j, i) of the cell, then tau, then the triangle number; a face is three int32 indices into the FULL
+ *                  vertex list.
+ *   degenerate     a corner that stores exactly 0 gives s = 0 or 1 and triangles of zero area; they are kept (the topology stays
+ *                  manifold).
+ * xyz [vertex_capacity,3] fp32, rgb [vertex_capacity,3] uint8 (NULL exactly when color is NULL), faces [face_capacity,3] int32, counts
+ * [2] int32 ON THE DEVICE: counts[0] = V and counts[1] = F always receive the full numbers (< 2^31 assumed).  Vertex rows >=
+ * vertex_capacity and face rows >= face_capacity are not written; a face row that is written holds the true indices even where they
+ * exceed vertex_capacity.  Both capacities >= 0.  workspace (4-byte aligned) >= um_tsdf_mesh_workspace_bytes(nx, ny, nz) (0 for bad
+ * sizes; 7 bytes per voxel and 16 per 256 voxels), else UM_ERR_WORKSPACE; every workspace byte that is read was written by the same
+ * call. */
+size_t um_tsdf_mesh_workspace_bytes(int nx, int ny, int nz);
+int um_tsdf_mesh(const float* tsdf, const float* weight, const float* color, int nx, int ny, int nz, const float* origin, float voxel,
+                 float min_weight, float* xyz, unsigned char* rgb, int* faces, int* counts, int vertex_capacity, int face_capacity,
+                 void* workspace, size_t ws_bytes, void* stream);
 
 /* Frame synthesis from flow (csrc/interp.hip): apply a flow to the frames it was computed from.  A classical synthesis with no learned
  * part.  Memory-bound, one thread per pixel; every entry point enqueues on `stream` and never synchronises; nothing is kept between

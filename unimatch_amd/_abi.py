@@ -118,6 +118,9 @@ SIGNATURES = {
     'um_tsdf_points_workspace_bytes': (_c_size_t, [_c_int] * 3),
     'um_tsdf_points': (_c_int, [_c_void_p] * 3 + [_c_int] * 3 + [ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 2 + [_c_void_p] * 3 +
                        [_c_int, _c_void_p, _c_size_t, _c_void_p]),
+    'um_tsdf_mesh_workspace_bytes': (_c_size_t, [_c_int] * 3),
+    'um_tsdf_mesh': (_c_int, [_c_void_p] * 3 + [_c_int] * 3 + [ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 2 + [_c_void_p] * 4 +
+                     [_c_int, _c_int, _c_void_p, _c_size_t, _c_void_p]),
     'um_instance_norm_fwd': (_c_int, [_c_void_p] * 3 + [ctypes.c_long, _c_int, ctypes.c_float, _c_int, _c_void_p]),
     'um_global_corr_workspace_bytes': (_c_size_t, [_c_int] * 4),
     'um_global_corr_softmax_flow': (_c_int, [_c_void_p] * 3 + [_c_int] * 6 + [_c_void_p, _c_size_t, _c_void_p]),

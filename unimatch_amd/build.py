@@ -14,10 +14,10 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libunimatch_hip.so')
 SOURCES = ['capi.hip', 'global_match.hip', 'window_attn.hip', 'local_ops.hip', 'linear.hip', 'ffn.hip', 'conv.hip', 'nhwc_ops.hip', 'norm_ops.hip', 'upsample.hip',
            'rccl_gather.hip', 'local_corr_mfma.hip', 'aliases.hip', 'probe.hip', 'video.hip', 'metrics.hip', 'prepost.hip', 'visualize.hip', 'geometry.hip', 'match_stats.hip',
-           'interp.hip', 'depth_multi.hip', 'fusion.hip']
+           'interp.hip', 'depth_multi.hip', 'fusion.hip', 'tsdf_mesh.hip']
 # hardware micro-benchmarks (um_debug_*): diagnostic builds only, never in the shipped library
 DIAG_SOURCES = ['microbench.hip']
-HEADERS = ['common.h', 'planes.h', 'timing.h', 'local_pixel.h', os.path.join('..', '..', 'include', 'unimatch_hip.h')]
+HEADERS = ['common.h', 'planes.h', 'timing.h', 'local_pixel.h', 'tsdf_grid.h', os.path.join('..', '..', 'include', 'unimatch_hip.h')]
 # per-file extras: the FFN kernel's hand-placed scalar VALU stream must not be re-packed into v_pk_* by the SLP vectorizer
 EXTRA_FLAGS = {'ffn.hip': ['-fno-slp-vectorize'], 'global_match.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form', '-Wno-inline-asm'], 'window_attn.hip': ['-fno-slp-vectorize'],
                'linear.hip': ['-fno-slp-vectorize'],
@@ -35,6 +35,8 @@ EXTRA_FLAGS = {'ffn.hip': ['-fno-slp-vectorize'], 'global_match.hip': ['-fno-slp
                'interp.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
                # ... and the TSDF fusion kernels theirs: the running averages of a voxel, bit for bit
                'fusion.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
+               # ... and the mesh vertices of the volume are, on the axis edges, bit for bit the points of fusion.hip
+               'tsdf_mesh.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
                # the confidence kernel's final quotients are IEEE: a row with one key gives max_prob = l / l = 1 exactly
                'match_stats.hip': ['-fno-slp-vectorize', '-fhip-fp32-correctly-rounded-divide-sqrt', '-Wno-inline-asm']}
 # kernels that sit at the register limit of their occupancy (conv_entry_kernel<Fp16, 2, 4>: all 256 VGPRs of two workgroups per CU): the
@@ -57,7 +59,11 @@ RESOURCE_GUARDS = {'conv.hip': {'conv_entry_kernel': 2},
                    'interp.hip': {'image_warp_kernel': 4, 'flow_splat_kernel': 4, 'splat_normalize_kernel': 4, 'frame_synth_kernel': 4},
                    # memory-bound per-voxel kernels, as the per-pixel ones of geometry.hip: no scratch, no wave lost to registers
                    'fusion.hip': {'tsdf_integrate_kernel': 4, 'tsdf_points_count_kernel': 4, 'tsdf_points_scan_kernel': 4,
-                                  'tsdf_points_scatter_kernel': 4}}
+                                  'tsdf_points_scatter_kernel': 4},
+                   # the marching-tetrahedra passes: per-voxel traversals of byte-sized codes, no scratch (the face pass keeps the vertex
+                   # bases and masks of a cell's seven edge owners in registers)
+                   'tsdf_mesh.hip': {'tsdf_mesh_cells_kernel': 4, 'tsdf_mesh_classify_kernel': 4, 'tsdf_mesh_scan_kernel': 4,
+                                     'tsdf_mesh_vertices_kernel': 4, 'tsdf_mesh_faces_kernel': 4}}
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result']
 
 

@@ -17,23 +17,13 @@
 // the order the host restatement of unimatch_amd/fusion.py evaluates them.
 #include "common.h"
 #include "timing.h"
+#include "tsdf_grid.h"
 
 extern void um_set_error(const char* fmt, ...);
 
 #define UM_TSDF_WG 256                         // threads = voxels per workgroup (four waves)
 #define UM_TSDF_SCAN_WG 1024                   // threads of the single scan workgroup (sixteen waves)
 #define UM_TSDF_FLT_MAX 3.402823466e+38f
-
-struct TsdfGrid {
-    int nx, ny, nz;
-    float ox, oy, oz, voxel;
-};
-
-static inline bool tsdf_dims_ok(int nx, int ny, int nz) {
-    return nx > 0 && ny > 0 && nz > 0 && (long)nx * ny < (1L << 31) && (long)nx * ny * nz < (1L << 31);
-}
-
-static inline bool tsdf_positive(float v) { return v > 0.f; }                 // false for NaN
 
 __device__ __forceinline__ bool tsdf_finite(float v) { return v <= UM_TSDF_FLT_MAX && v >= -UM_TSDF_FLT_MAX; }       // false for NaN
 

@@ -37,6 +37,9 @@ Values and geometry (both modes write the same files):
                             The integration weight is the ``keep`` mask of the point cloud -- consistency, plus ``--min-confidence``
                             when given -- so the surface is made of exactly the pixels ``--save-ply`` keeps, averaged across frames
                             instead of concatenated; it needs no ``--save-ply``
+  ``--save-tsdf-mesh FILE`` the triangle mesh of that TSDF volume (binary PLY with a face element, :func:`unimatch_amd.io.write_ply_mesh`):
+                            marching tetrahedra over the same volume, with the same ``--voxel-size``, ``--tsdf-trunc``,
+                            ``--tsdf-min-weight`` and ``--min-confidence``; with ``--save-tsdf-ply`` as well, one volume serves both
 
 Frame i has a depth map through the pair (i, i + 1); the last frame has one only with ``--pred-bidir-depth``, through the last pair's
 backward prediction, and gets its ``_depth.png`` / ``_occ.png`` then.  The geometry always uses the depth restored to the frames' own
@@ -80,13 +83,14 @@ class _SceneCollector:
     arrives and, for the latter two, keeps it and its uint8 frame on the device until :meth:`finish` fuses the scene."""
 
     def __init__(self, out_dir, imgs, poses, k, save_depth, consistency_check, save_ply, ply_stride, min_views, px_thr, rel_thr,
-                 min_confidence=None, save_tsdf_ply=None, voxel_size=0.04, tsdf_trunc=None, tsdf_min_weight=1.):
+                 min_confidence=None, save_tsdf_ply=None, voxel_size=0.04, tsdf_trunc=None, tsdf_min_weight=1., save_tsdf_mesh=None):
         self.min_confidence, self.conf = min_confidence, []
+        self.save_tsdf_mesh = save_tsdf_mesh
         self.save_tsdf_ply, self.voxel_size, self.tsdf_trunc, self.tsdf_min_weight = save_tsdf_ply, voxel_size, tsdf_trunc, tsdf_min_weight
         self.out_dir, self.imgs, self.poses, self.k = out_dir, imgs, poses, k
         self.save_depth, self.consistency_check, self.save_ply = save_depth, consistency_check, save_ply
         self.ply_stride, self.min_views, self.px_thr, self.rel_thr = ply_stride, min_views, px_thr, rel_thr
-        self.fuse = bool(consistency_check or save_ply or save_tsdf_ply)
+        self.fuse = bool(consistency_check or save_ply or save_tsdf_ply or save_tsdf_mesh)
         self.depths, self.frames = [], []
 
     def stem(self, i):
@@ -129,26 +133,35 @@ class _SceneCollector:
                 write_png8(self.stem(i) + '_occ.png', occ[i])
         if self.save_ply:
             write_ply(self.save_ply, out['xyz'].cpu().numpy(), out['rgb'].cpu().numpy())
-        if self.save_tsdf_ply:
+        if self.save_tsdf_ply or self.save_tsdf_mesh:
             from .fusion import fuse_depth_sequence_tsdf
+            from .io import write_ply_mesh
             if not bool(out['keep'].any()):                    # nothing is kept: an empty surface, as --save-ply writes an empty cloud
-                write_ply(self.save_tsdf_ply, np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8))
+                if self.save_tsdf_ply:
+                    write_ply(self.save_tsdf_ply, np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8))
+                if self.save_tsdf_mesh:
+                    write_ply_mesh(self.save_tsdf_mesh, np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8), np.zeros((0, 3), np.int32))
                 return
             surf = fuse_depth_sequence_tsdf(depths, torch.from_numpy(self.k)[None].to(dev), torch.from_numpy(self.poses[:n]).to(dev), colors,
                                             weight=out['keep'], voxel_size=self.voxel_size, trunc=self.tsdf_trunc,
-                                            min_weight=self.tsdf_min_weight)
-            write_ply(self.save_tsdf_ply, surf['xyz'].cpu().numpy(), surf['rgb'].cpu().numpy())
+                                            min_weight=self.tsdf_min_weight, mesh=bool(self.save_tsdf_mesh))
+            if self.save_tsdf_mesh:
+                write_ply_mesh(self.save_tsdf_mesh, surf['xyz'].cpu().numpy(), surf['rgb'].cpu().numpy(), surf['faces'].cpu().numpy())
+            if self.save_tsdf_ply:                             # the points of the same volume
+                xyz, rgb = surf['volume'].extract_points(self.tsdf_min_weight) if self.save_tsdf_mesh else (surf['xyz'], surf['rgb'])
+                write_ply(self.save_tsdf_ply, xyz.cpu().numpy(), rgb.cpu().numpy())
 
 
 def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_size=None, min_depth=0.5, max_depth=10.,
               num_depth_candidates=64, depth_from_argmax=False, pred_bidir_depth=False, scale_intrinsics=False, device='cuda',
               pairs_per_launch=None, save_depth=False, consistency_check=False, save_ply=None, ply_stride=1, min_views=1, px_thr=1.0,
               rel_thr=0.01, save_confidence=False, min_confidence=None, peak_radius=1, fuse_neighbours=False, save_tsdf_ply=None,
-              voxel_size=0.04, tsdf_trunc=None, tsdf_min_weight=1.):
+              voxel_size=0.04, tsdf_trunc=None, tsdf_min_weight=1., save_tsdf_mesh=None):
     """``inference_depth`` over the scene: returns the number of frames written (one less than the scene has).
     ``pairs_per_launch=N``: sequence mode (the module docstring), in pieces of N pairs; ``None``: one ``predict`` per pair.
     ``save_depth``, ``consistency_check``, ``save_ply`` (a file name): the value and geometry outputs of the module docstring.
     ``save_tsdf_ply`` (a file name), ``voxel_size``, ``tsdf_trunc``, ``tsdf_min_weight``: the TSDF surface of the scene.
+    ``save_tsdf_mesh`` (a file name): the triangle mesh of the same volume, with the same parameters.
     ``save_confidence``, ``min_confidence`` (with ``save_ply`` or ``save_tsdf_ply``), ``peak_radius``: the plane sweep's confidence, taken in the forward's
     own matching launch (``forward_with_depth_confidence`` / ``forward_sequence(return_confidence=True)``).
     ``fuse_neighbours`` (sequence mode only, not with ``pred_bidir_depth``): the previous frame votes in every frame's plane sweep
@@ -156,8 +169,8 @@ def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_si
     from .confidence import confidence_to_image, confidence_to_image_size
     from .io import write_png8
     from .prepost import InferenceGeometry
-    if min_confidence is not None and not (save_ply or save_tsdf_ply):
-        raise ValueError('min_confidence filters the point cloud: it needs save_ply or save_tsdf_ply')
+    if min_confidence is not None and not (save_ply or save_tsdf_ply or save_tsdf_mesh):
+        raise ValueError('min_confidence filters the point cloud: it needs save_ply, save_tsdf_ply or save_tsdf_mesh')
     if fuse_neighbours and pairs_per_launch is None:
         raise ValueError('fuse_neighbours is an option of the sequence mode: it needs pairs_per_launch')
     if fuse_neighbours and pred_bidir_depth:
@@ -166,11 +179,11 @@ def run_depth(model, scene_dir, out_dir, fwd_kw, padding_factor=16, inference_si
     imgs, poses, k = read_scene(scene_dir)
     os.makedirs(out_dir, exist_ok=True)
     collect = None
-    if save_depth or consistency_check or save_ply or save_tsdf_ply:
+    if save_depth or consistency_check or save_ply or save_tsdf_ply or save_tsdf_mesh:
         collect = _SceneCollector(out_dir, imgs, poses, k, save_depth, consistency_check, save_ply, int(ply_stride), int(min_views),
                                   float(px_thr), float(rel_thr), None if min_confidence is None else float(min_confidence),
                                   save_tsdf_ply, float(voxel_size), None if tsdf_trunc is None else float(tsdf_trunc),
-                                  float(tsdf_min_weight))
+                                  float(tsdf_min_weight), save_tsdf_mesh)
     skip = ('task', 'min_depth', 'max_depth', 'num_depth_candidates', 'depth_from_argmax', 'pred_bidir_depth', 'intrinsics', 'pose',
             'poses')
     fwd_kw = {key: v for key, v in fwd_kw.items() if key not in skip}
@@ -314,6 +327,8 @@ def main(argv=None):
     ap.add_argument('--ply-stride', type=int, default=1, metavar='S', help='every S-th pixel of every row and column goes into the cloud')
     ap.add_argument('--save-tsdf-ply', default=None, metavar='FILE',
                     help='write the TSDF surface of the scene: the pixels --save-ply keeps, fused in one voxel grid')
+    ap.add_argument('--save-tsdf-mesh', default=None, metavar='FILE',
+                    help='write the triangle mesh of the TSDF volume of the scene (the options of --save-tsdf-ply apply)')
     ap.add_argument('--voxel-size', type=float, default=0.04, metavar='M', help='with --save-tsdf-ply: the edge of a voxel in metres')
     ap.add_argument('--tsdf-trunc', type=float, default=None, metavar='M', help='with --save-tsdf-ply: the truncation distance (default: 4 voxels)')
     ap.add_argument('--tsdf-min-weight', type=float, default=1., metavar='W',
@@ -342,7 +357,7 @@ def main(argv=None):
                   scale_intrinsics=args.scale_intrinsics, pairs_per_launch=args.pairs_per_launch, save_depth=args.save_depth,
                   consistency_check=args.consistency_check, save_ply=args.save_ply, ply_stride=args.ply_stride, min_views=args.min_views,
                   px_thr=args.px_thr, rel_thr=args.rel_thr, save_confidence=args.save_confidence, min_confidence=args.min_confidence,
-                  peak_radius=args.peak_radius, fuse_neighbours=args.fuse_neighbours, save_tsdf_ply=args.save_tsdf_ply,
+                  peak_radius=args.peak_radius, fuse_neighbours=args.fuse_neighbours, save_tsdf_ply=args.save_tsdf_ply, save_tsdf_mesh=args.save_tsdf_mesh,
                   voxel_size=args.voxel_size, tsdf_trunc=args.tsdf_trunc, tsdf_min_weight=args.tsdf_min_weight)
     print(f'{n} frames written to {args.out}')
 

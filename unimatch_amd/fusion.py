@@ -1,7 +1,7 @@
 """Volumetric (TSDF) fusion of posed depth maps: one voxel grid averages the per-frame depths, weighted, and yields one surface.
 
   TSDFVolume(origin, voxel_size, dims, trunc, max_weight, with_color)   the volume state and its three operations: ``integrate``,
-                                                                        ``extract_points``, ``reset``
+                                                                        ``extract_points``, ``extract_mesh``, ``reset``
   volume_bounds(depths, intrinsics, poses, keep, ...)                   the axis-aligned box of the kept back-projected points
   fuse_depth_sequence_tsdf(depths, intrinsics, poses, colors, weight)   a posed video fused into one volume, in chunks of views, and
                                                                         its surface points: ``dict(xyz, rgb, volume)``
@@ -39,6 +39,10 @@ of a bidirectional camera pack of the intrinsics and the camera-to-world pose):
 the neighbour ``n = p + e_a`` inside the volume, a crossing iff both weights are ``>= min_weight``, ``(tp < 0) != (tn < 0)`` and
 ``|tp| < 1``, ``|tn| < 1`` (which drops free-space-to-unseen jumps at occlusion borders).  With ``s = tp / (tp - tn)`` its point is
 ``X(p)`` with coordinate ``a`` increased by ``s voxel``, its colour ``rint(Cp + s (Cn - Cp))`` clamped to 0..255.
+
+``extract_mesh`` (``csrc/tsdf_mesh.hip``, ``um_tsdf_mesh``): marching tetrahedra on the Kuhn split of every cell whose eight corners are
+valid; the definition is written out at ``um_tsdf_mesh`` in ``include/unimatch_hip.h`` and restated by :func:`extract_mesh_host`.  Its
+vertices on the axis edges are bit for bit points of ``extract_points``.
 """
 import ctypes
 import math
@@ -180,6 +184,121 @@ def extract_points_host(tsdf, weight, color=None, *, origin, voxel, min_weight=1
     return xyz, rgb.t().contiguous()
 
 
+# ------------------------------------------------------------------ host restatement: the mesh
+_TET_PERMS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+_TET_POSITIVE = (True, False, False, True, True, False)
+_TET_EDGES = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))                  # the six edges of a tetrahedron, by corner position
+
+
+def _tet_corners(tau):
+    """The four corner masks of tetrahedron ``tau``: 0, one step, two steps, 7."""
+    p = _TET_PERMS[tau]
+    return 0, 1 << p[0], (1 << p[0]) | (1 << p[1]), 7
+
+
+def _tet_triangles(pattern, positive):
+    """The triangles of a tetrahedron whose corner ``q`` is inside iff bit ``q`` of ``pattern`` is set: a list of triples of edge
+    numbers (indices into ``_TET_EDGES``)."""
+    ins = [q for q in range(4) if pattern >> q & 1]
+    outs = [q for q in range(4) if not pattern >> q & 1]
+    edge = lambda q, r: _TET_EDGES.index((min(q, r), max(q, r)))
+    if len(ins) == 1:
+        a = ins[0]
+        tris, rev = [[edge(a, o) for o in outs]], positive == (a % 2 == 1)
+    elif len(ins) == 3:
+        a = outs[0]
+        tris, rev = [[edge(a, i) for i in ins]], not positive == (a % 2 == 1)
+    elif len(ins) == 2:
+        (a, b), (c, d) = ins, outs
+        q = [edge(a, c), edge(a, d), edge(b, d), edge(b, c)]
+        tris, rev = [[q[0], q[1], q[2]], [q[0], q[2], q[3]]], positive == ((a + b) % 2 == 0)
+    else:
+        return []
+    return [t[::-1] for t in tris] if rev else tris
+
+
+def _shifted(t, m, cells):
+    """``t [nz, ny, nx]`` seen from every cell (``cells = True``: ``[nz - 1, ny - 1, nx - 1]``) at the corner mask ``m``."""
+    nz, ny, nx = t.shape
+    dk, dj, di = m >> 2 & 1, m >> 1 & 1, m & 1
+    if cells:
+        return t[dk:nz - 1 + dk, dj:ny - 1 + dj, di:nx - 1 + di]
+    return t[dk:, dj:, di:]
+
+
+def mesh_edges_host(tsdf, weight, min_weight=1.):
+    """``(active [nz - 1, ny - 1, nx - 1], sel [nz, ny, nx, 7])``, both boolean: the active cells of ``um_tsdf_mesh`` and the owned
+    edges that carry a vertex (last index: ``e - 1``)."""
+    nz, ny, nx = tsdf.shape
+    mw = _scalar(min_weight, tsdf)
+    valid = (weight >= mw) & (tsdf.abs() < 1)
+    inside = tsdf < 0
+    active = _shifted(valid, 0, True).clone()
+    for m in range(1, 8):
+        active &= _shifted(valid, m, True)
+    act = torch.zeros_like(valid)                            # on the voxel grid: False where the voxel is no cell
+    act[:nz - 1, :ny - 1, :nx - 1] = active
+    sel = []
+    for e in range(1, 8):
+        has = torch.zeros_like(valid)                        # at least one cell p - s of the edge is active
+        for s in range(8):
+            if s & e:
+                continue
+            dk, dj, di = s >> 2 & 1, s >> 1 & 1, s & 1
+            has[dk:, dj:, di:] |= act[:nz - dk, :ny - dj, :nx - di]
+        cross = torch.zeros_like(valid)
+        ek, ej, ei = e >> 2 & 1, e >> 1 & 1, e & 1
+        cross[:nz - ek, :ny - ej, :nx - ei] = inside[:nz - ek, :ny - ej, :nx - ei] != _shifted(inside, e, False)
+        sel.append(has & cross)
+    return active, torch.stack(sel, -1)
+
+
+def extract_mesh_host(tsdf, weight, color=None, *, origin, voxel, min_weight=1.):
+    """``um_tsdf_mesh`` step by step, in the dtype of ``tsdf``: ``(xyz [V, 3], rgb [V, 3] uint8 or None, faces [F, 3] int64)`` -- marching
+    tetrahedra on the Kuhn split (the definition: ``include/unimatch_hip.h``), vertices in ascending ``(k, j, i, e)``, faces in ascending
+    ``(k, j, i)`` of the cell, then by tetrahedron, then by triangle, counter-clockwise seen from free space.  A corner that stores
+    exactly 0 gives ``s`` of 0 or 1 and triangles of zero area; they are KEPT, because the topology stays manifold with them.  In float32
+    this is bitwise the device result, in float64 the reference."""
+    dt, dev = tsdf.dtype, tsdf.device
+    nz, ny, nx = tsdf.shape
+    if min(nx, ny, nz) < 2:                                  # no cell
+        return (torch.zeros((0, 3), dtype=dt, device=dev), None if color is None else torch.zeros((0, 3), dtype=torch.uint8, device=dev),
+                torch.zeros((0, 3), dtype=torch.int64, device=dev))
+    active, sel = mesh_edges_host(tsdf, weight, min_weight)
+    k, j, i, a = sel.nonzero(as_tuple=True)                                                # ascending (k, j, i, e)
+    e = a + 1
+    vid = (sel.reshape(-1).cumsum(0) - 1).reshape(sel.shape)                               # the index of every vertex, at its edge
+    vs = _scalar(voxel, tsdf)
+    base = [_scalar(origin[0], tsdf) + i.to(dt) * vs, _scalar(origin[1], tsdf) + j.to(dt) * vs, _scalar(origin[2], tsdf) + k.to(dt) * vs]
+    tp = tsdf[k, j, i]
+    kn, jn, in_ = k + (e >> 2 & 1), j + (e >> 1 & 1), i + (e & 1)
+    tn = tsdf[kn, jn, in_]
+    s = tp / (tp - tn)
+    xyz = torch.stack([torch.where((e >> ax & 1) == 1, base[ax] + s * vs, base[ax]) for ax in range(3)], 1)
+    rgb = None
+    if color is not None:
+        cp, cn = color[:, k, j, i], color[:, kn, jn, in_]
+        val = cp + s * (cn - cp)
+        rgb = torch.where(val == val, torch.round(val), torch.zeros_like(val)).clamp(0.0, 255.0).to(torch.uint8).t().contiguous()
+    # faces: the active cells whose corners are not all on one side, in ascending (k, j, i)
+    inside = tsdf < 0
+    ins = torch.stack([_shifted(inside, m, True) for m in range(8)], -1)                   # [cells, 8]
+    ck, cj, ci = (active & ins.any(-1) & ~ins.all(-1)).nonzero(as_tuple=True)
+    ins = ins[ck, cj, ci].long()
+    rows, keep = [], []
+    for tau in range(6):
+        v = _tet_corners(tau)
+        pattern = sum(ins[:, v[q]] << q for q in range(4))
+        edges = torch.stack([vid[ck + (v[q] >> 2 & 1), cj + (v[q] >> 1 & 1), ci + (v[q] & 1), (v[r] ^ v[q]) - 1] for q, r in _TET_EDGES], 1)
+        table = [_tet_triangles(p, _TET_POSITIVE[tau]) for p in range(16)]
+        count = torch.tensor([len(t) for t in table], device=dev)
+        which = torch.tensor([sum(t, []) + [0] * (6 - 3 * len(t)) for t in table], device=dev)       # [16, 6] edge numbers
+        rows.append(edges.gather(1, which[pattern]).reshape(-1, 2, 3))
+        keep.append(count[pattern][:, None] > torch.arange(2, device=dev))
+    faces = torch.stack(rows, 1)[torch.stack(keep, 1)]                                     # [cells, 6, 2, 3] -> cell, tau, triangle
+    return xyz, rgb, faces.reshape(-1, 3)
+
+
 # ------------------------------------------------------------------ the library
 def _ptr(t):
     return None if t is None else t.data_ptr()
@@ -247,6 +366,34 @@ def points_device(tsdf, weight, color, *, origin, voxel, min_weight=1., capacity
                                       float(min_weight), xyz.data_ptr(), _ptr(rgb if color is not None else None), count.data_ptr(),
                                       capacity, ws.data_ptr(), nbytes, _stream()), 'um_tsdf_points')
     return xyz, (rgb if color is not None else None), count
+
+
+def mesh_device(tsdf, weight, color, *, origin, voxel, min_weight=1., vertex_capacity, face_capacity, xyz=None, rgb=None, faces=None):
+    """``um_tsdf_mesh`` on CUDA tensors: ``(xyz [vertex_capacity, 3], rgb [vertex_capacity, 3] or None, faces [face_capacity, 3] int32,
+    counts)``, ``counts`` a two-element int32 tensor ON THE DEVICE holding the full ``(V, F)``; vertex rows ``min(V, vertex_capacity)..``
+    and face rows ``min(F, face_capacity)..`` are unwritten, and a written face row holds the indices into the full vertex list.
+    ``xyz`` / ``rgb`` / ``faces``: buffers to write into (fresh ones otherwise).  No synchronisation."""
+    lib = _abi.load()                        # raises when the HIP extension is missing: there is no silent fallback
+    _check_state('mesh_device', tsdf, weight, color)
+    nz, ny, nx = tsdf.shape
+    vcap, fcap, dev = int(vertex_capacity), int(face_capacity), tsdf.device
+    with torch.cuda.device(dev):
+        xyz = torch.empty((vcap, 3), dtype=torch.float32, device=dev) if xyz is None else xyz
+        faces = torch.empty((fcap, 3), dtype=torch.int32, device=dev) if faces is None else faces
+        if color is not None and rgb is None:
+            rgb = torch.empty((vcap, 3), dtype=torch.uint8, device=dev)
+        if tuple(xyz.shape) != (vcap, 3) or xyz.dtype != torch.float32 or not xyz.is_contiguous() or (
+                rgb is not None and (tuple(rgb.shape) != (vcap, 3) or rgb.dtype != torch.uint8 or not rgb.is_contiguous())):
+            raise ValueError(f'mesh_device: expected xyz float32 and rgb uint8 as contiguous [{vcap}, 3] buffers')
+        if tuple(faces.shape) != (fcap, 3) or faces.dtype != torch.int32 or not faces.is_contiguous():
+            raise ValueError(f'mesh_device: expected faces as a contiguous int32 [{fcap}, 3] buffer')
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        nbytes = lib.um_tsdf_mesh_workspace_bytes(nx, ny, nz)
+        ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+        _abi.check(lib.um_tsdf_mesh(tsdf.data_ptr(), weight.data_ptr(), _ptr(color), nx, ny, nz, _origin3(origin), float(voxel),
+                                    float(min_weight), xyz.data_ptr(), _ptr(rgb if color is not None else None), faces.data_ptr(),
+                                    counts.data_ptr(), vcap, fcap, ws.data_ptr(), nbytes, _stream()), 'um_tsdf_mesh')
+    return xyz, (rgb if color is not None else None), faces, counts
 
 
 # ------------------------------------------------------------------ public interface
@@ -323,6 +470,32 @@ class TSDFVolume:
             xyz, rgb, _ = points_device(self.tsdf, self.weight, self.color, min_weight=min_weight, capacity=n, **self._grid())
         return xyz[:n], None if rgb is None else rgb[:n]
 
+    def _mesh_capacities(self):
+        nx, ny, nz = self.dims
+        sheets = 6 * (nx * ny + ny * nz + nx * nz)
+        return 4 * sheets, 8 * sheets
+
+    def extract_mesh(self, min_weight=1.):
+        """``(xyz [V, 3] float32, rgb [V, 3] uint8 or None, faces [F, 3])``: the triangle mesh of the volume between voxels of weight
+        ``>= min_weight`` -- marching tetrahedra on the Kuhn split (:func:`extract_mesh_host`), every face counter-clockwise seen from
+        free space; ``faces`` is int32 on the device and int64 on the host.  Zero-area triangles (a corner storing exactly 0) are kept.
+        On the device: ONE synchronisation (the read of V and F) after a run at default capacities, and one more run at exactly
+        ``(V, F)`` only when either count exceeds its capacity.  The defaults: ``extract_points`` allows ``6 (nx ny + ny nz + nx nz)``
+        rows -- six sheets that each project one-to-one onto a side of the box, at one axis crossing per unit of projected area.  A
+        sheet with unit normal ``n`` crosses ``|n . d|`` edges of direction ``d`` per unit area, and each axis occurs in four of the
+        seven edge directions, so the mesh has at most four vertices per unit of projected area: four times the rows of the points.  A
+        surface has ``F = 2 (V - chi) - boundary edges``, so twice as many face rows as vertex rows."""
+        if self.tsdf.device.type != 'cuda':
+            return extract_mesh_host(self.tsdf, self.weight, self.color, min_weight=min_weight, **self._grid())
+        vcap, fcap = self._mesh_capacities()
+        xyz, rgb, faces, counts = mesh_device(self.tsdf, self.weight, self.color, min_weight=min_weight, vertex_capacity=vcap,
+                                              face_capacity=fcap, **self._grid())
+        v, f = (int(n) for n in counts.tolist())                                   # the one synchronisation
+        if v > vcap or f > fcap:
+            xyz, rgb, faces, _ = mesh_device(self.tsdf, self.weight, self.color, min_weight=min_weight, vertex_capacity=v, face_capacity=f,
+                                             **self._grid())                       # a mesh with a face has a vertex: neither is 0
+        return xyz[:v], None if rgb is None else rgb[:v], faces[:f]
+
 
 def volume_bounds(depths, intrinsics, poses, keep=None, min_depth=0., max_depth=float('inf'), stride=4, margin=0.):
     """``(lo, hi)``, two tuples of three floats: the axis-aligned world box of the back-projected pixels of ``depths [T, H, W]`` that
@@ -341,8 +514,9 @@ def _grid_dims(lo, hi, voxel):
 
 def fuse_depth_sequence_tsdf(depths, intrinsics, poses, colors=None, weight=None, voxel_size=0.04, trunc=None, max_weight=64.,
                              min_weight=1., views_per_launch=8, max_voxels=2 ** 28, min_depth=0., max_depth=float('inf'),
-                             bounds_stride=4):
-    """The TSDF surface of a posed video: ``dict(xyz [N, 3], rgb [N, 3] or None, volume)``.
+                             bounds_stride=4, mesh=False):
+    """The TSDF surface of a posed video: ``dict(xyz [N, 3], rgb [N, 3] or None, volume)``; with ``mesh=True`` the dict also holds
+    ``faces [F, 3]`` and ``xyz`` / ``rgb`` are the vertices of the triangle mesh (:meth:`TSDFVolume.extract_mesh`).
 
     ``depths [T, H, W]`` metric, ``intrinsics [1 or T, 3, 3]``, ``poses [T, 4, 4]`` camera-to-world, ``colors [T, H, W, 3]`` uint8,
     ``weight [T, H, W]`` the per-pixel integration weight (the ``keep`` mask of ``fuse_depth_sequence``, a confidence, ...; <= 0: the
@@ -381,5 +555,8 @@ def fuse_depth_sequence_tsdf(depths, intrinsics, poses, colors=None, weight=None
     for a in range(0, t, step):
         volume.integrate(depths[a:a + step], k[a:a + step], p[a:a + step], None if weight is None else weight[a:a + step],
                          None if colors is None else colors[a:a + step], min_depth, max_depth)
+    if mesh:
+        xyz, rgb, faces = volume.extract_mesh(min_weight)
+        return {'xyz': xyz, 'rgb': rgb, 'faces': faces, 'volume': volume}
     xyz, rgb = volume.extract_points(min_weight)
     return {'xyz': xyz, 'rgb': rgb, 'volume': volume}

@@ -238,6 +238,64 @@ def read_ply(filename):
     return xyz, rgb
 
 
+# ------------------------------------------------------------------ PLY triangle meshes
+_PLY_FACE = [('n', 'u1'), ('a', '<i4'), ('b', '<i4'), ('c', '<i4')]
+_PLY_FACE_PROP = 'property list uchar int vertex_indices'
+
+
+def write_ply_mesh(filename, xyz, rgb, faces):
+    """A binary little-endian PLY of a triangle mesh: the vertex element exactly as :func:`write_ply` writes it (``rgb`` may be
+    ``None``), then ``element face F`` with ``property list uchar int vertex_indices`` -- F packed rows of 13 bytes (the count 3 and
+    three int32 indices).  ``faces [F, 3]`` of an integer type, every index in ``0 .. N - 1``."""
+    faces = np.asarray(faces)
+    n = np.asarray(xyz).shape[0]
+    if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.kind not in 'iu':
+        raise ValueError(f'faces must be integers [F, 3], got {faces.dtype} {faces.shape}')
+    if faces.size and (int(faces.min()) < 0 or int(faces.max()) >= n):
+        raise ValueError(f'faces must index the {n} vertices, got indices in {int(faces.min())} .. {int(faces.max())}')
+    rows = np.empty(faces.shape[0], dtype=_PLY_FACE)
+    rows['n'] = 3
+    for j, (name, _) in enumerate(_PLY_FACE[1:]):
+        rows[name] = faces[:, j]
+    write_ply(filename, xyz, rgb)
+    with open(filename, 'rb') as f:
+        head, end, body = f.read().partition(b'end_header\n')
+    with open(filename, 'wb') as f:
+        f.write(head + f'element face {faces.shape[0]}\n{_PLY_FACE_PROP}\n'.encode('ascii') + end + body)
+        f.write(rows.tobytes())
+
+
+def read_ply_mesh(filename):
+    """``(xyz [N, 3] float32, rgb [N, 3] uint8 or None, faces [F, 3] int32)`` of a file :func:`write_ply_mesh` wrote."""
+    with open(filename, 'rb') as f:
+        blob = f.read()
+    end = blob.find(b'end_header\n')
+    if not blob.startswith(b'ply\n') or end < 0:
+        raise ValueError('not a PLY file')
+    lines = blob[:end].decode('ascii').split('\n')
+    if lines[1] != 'format binary_little_endian 1.0':
+        raise ValueError('only binary little-endian PLY files are supported')
+    elements = [ln for ln in lines if ln.startswith('element ')]
+    if len(elements) != 2 or not elements[0].startswith('element vertex ') or not elements[1].startswith('element face '):
+        raise ValueError(f'expected the elements vertex and face, got {elements}')
+    n, nf = int(elements[0].split()[-1]), int(elements[1].split()[-1])
+    at = lines.index(elements[1])
+    props = [tuple(ln.split()[1:]) for ln in lines[:at] if ln.startswith('property ')]
+    xyz_props, rgb_props = [(_PLY_TYPES[k], nm) for nm, k in _PLY_XYZ], [(_PLY_TYPES[k], nm) for nm, k in _PLY_RGB]
+    if props not in (xyz_props, xyz_props + rgb_props) or [ln for ln in lines[at + 1:] if ln] != [_PLY_FACE_PROP]:
+        raise ValueError(f'unsupported PLY mesh properties: {props}, {lines[at + 1:]}')
+    fields = _PLY_XYZ + (_PLY_RGB if len(props) == 6 else [])
+    start = end + len(b'end_header\n')
+    rows = np.frombuffer(blob, dtype=fields, count=n, offset=start)
+    tris = np.frombuffer(blob, dtype=_PLY_FACE, count=nf, offset=start + rows.nbytes)
+    xyz = np.stack([rows[name] for name, _ in _PLY_XYZ], 1).astype(np.float32)
+    rgb = np.stack([rows[name] for name, _ in _PLY_RGB], 1) if len(props) == 6 else None
+    faces = np.stack([tris[name] for name, _ in _PLY_FACE[1:]], 1).astype(np.int32).reshape(-1, 3)
+    if nf and (not (tris['n'] == 3).all() or faces.min() < 0 or faces.max() >= n):
+        raise ValueError('only triangles that index the vertex element are supported')
+    return xyz, rgb, faces
+
+
 # ------------------------------------------------------------------ KITTI encodings
 def write_kitti_flow(filename, uv):
     """uv: [H, W, 2].  Stored RGB = (64 u + 2^15, 64 v + 2^15, valid = 1)."""
